@@ -13,6 +13,11 @@ One step = ViT encode (frozen SigLIP + DINOv2) -> pool -> projector -> scatter -
 shifted CE (+L2Wrap) -> backward -> bucketed reduce-scatter -> clip 1.0 -> fused AdamW -> all-gather, on a
 synthetic LLaVA-style batch (576 image tokens + 2048 text tokens = 2624 tokens per sample, bf16), random-init
 weights of the VisualRWKV-7 1.5B architecture (L24 C2048 H32, vocab 65536).  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step`: one timed step).  `--full` adds what
+the headline does not need: the grad_cp 1 / 2 companions, the WKV7 roofline (per-launch HIP events during the timed
+steps, the stream-copy ceiling, the committed PMC traffic), the CPU baseline and, N > 1, the communication report.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -235,6 +240,33 @@ class _StdoutToStderr:
         os.close(self._saved)
 
 
+def dump_outputs(dirname, model, loss, gnorm, n_sample=1 << 22, seed=1234):
+    """--dump-outputs: what the last timed step handed its caller, for comparing two builds output for output -- loss.npy and
+    grad_norm.npy (the pre-clip global norm engine.step() returned; float64) and, over the trainable parameters in
+    named_parameters() order, params.npy (as AdamW left them) and grads.npy (that step's gradients), float32.  When they hold
+    more than n_sample elements in all, each parameter contributes a fixed seeded sample of its elements (at least 256, or all)."""
+    import numpy as np
+    named = [p for _, p in model.named_parameters() if p.requires_grad]
+    total = sum(p.numel() for p in named)
+    g = torch.Generator().manual_seed(seed)
+    params, grads = [], []
+    for p in named:
+        k = p.numel() if total <= n_sample else min(p.numel(), max(256, -(-n_sample * p.numel() // total)))
+        if k == p.numel():
+            idx = torch.arange(k)
+        else:
+            idx = torch.randint(0, p.numel(), (k,), generator=g).sort().values
+        idx = idx.to(p.device)
+        params.append(p.detach().reshape(-1)[idx].float().cpu())
+        grads.append(torch.zeros(k) if p.grad is None else p.grad.detach().reshape(-1)[idx].float().cpu())      # None: unused in the step
+    os.makedirs(dirname, exist_ok=True)
+    out = {"loss": np.array([float(loss.detach())], dtype=np.float64), "grad_norm": np.array([float(gnorm)], dtype=np.float64),
+           "params": torch.cat(params).numpy(), "grads": torch.cat(grads).numpy()}
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    for name, v in out.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), v)
+
+
 def _wkv7_kernel_name(backward: int, B: int, T: int, H: int) -> str:
     """The kernel a WKV7 launch of this shape resolves to (vrwkv_wkv7_resolve_variant: a pure function of the shape and the A/B override --
     the launches themselves come from two threads, the Python thread and autograd's): what the roofline entry is about.
@@ -277,6 +309,10 @@ def main():
                     help="loader: synthetic JPEGs on disk -> data.MyDataset workers -> DevicePrefetcher (train.py:219-222)")
     ap.add_argument("--loader-workers", type=int, default=8)
     ap.add_argument("--async-gather", type=int, default=1, help="overlap the parameter all-gather with the next ViT encode")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: grad_cp companions, WKV7 roofline, CPU baseline, N > 1 comm report")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write the loss, gradient norm and sampled parameters / gradients of the last one as DIR/<name>.npy")
     a = ap.parse_args()
     cpu_mode = a.backend == "gloo"
     if cpu_mode and a.model not in ("tiny", "0b1"):
@@ -367,8 +403,8 @@ def main():
         engine.zero_grad()
         loss = model.training_step(batch)
         loss.backward()
-        engine.step(2e-5)
-        return loss
+        gnorm = engine.step(2e-5)
+        return loss, gnorm
 
     def fence():
         if world > 1:
@@ -387,15 +423,18 @@ def main():
         with open(a.profile_ops, "w") as f:
             f.write(prof.key_averages(group_by_input_shape=True).table(sort_by="cuda_time_total", row_limit=400, max_name_column_width=50,
                                                                        max_shapes_column_width=90))
-    wkv7.EVENT_LOG = [] if rank == 0 else None
-    if engine.collective and engine.overlap:
+    wkv7.EVENT_LOG = [] if rank == 0 and a.full else None
+    if a.full and engine.collective and engine.overlap:
         engine.comm_timing = []                     # exposed-communication estimate from stream events (dp.Zero1Engine.comm_report)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = step()
+        loss, gnorm = step()
     fence()
     dt = time.perf_counter() - t0
-    log, wkv7.EVENT_LOG = wkv7.EVENT_LOG, None
+    log, wkv7.EVENT_LOG = wkv7.EVENT_LOG or [], None
+    if a.dump_outputs and rank == 0:
+        engine.wait_params()
+        dump_outputs(a.dump_outputs, model, loss, gnorm)
     tmax = torch.tensor([dt], device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -411,7 +450,7 @@ def main():
     comm = engine.comm_report(a.steps) if engine.comm_timing else None
     engine.comm_timing = None
     cp_ref = cp_sel = None
-    if a.grad_cp == 0 and not a.no_grad_cp_companion and not cpu_mode:
+    if a.full and a.grad_cp == 0 and not a.no_grad_cp_companion and not cpu_mode:
         def companion(mode, n):
             args.grad_cp = mode
             step(); fence()
@@ -485,7 +524,7 @@ def main():
                     out["roofline"]["traffic"] = rec["hbm_bytes_per_launch"]
                     out["roofline"]["traffic_kernel"] = rec.get("kernel")       # the kernel the counters were collected on (must be the one named in "kernel")
                     out["roofline"]["traffic_source"] = "profiles/wkv7_pmc.json (separate rocprofv3 --pmc passes of benchmarks/wkv7_pmc.sh, same shape)"
-        if world == 1 and not a.no_cpu_baseline and not cpu_mode:
+        if a.full and world == 1 and not a.no_cpu_baseline and not cpu_mode:
             out["cpu_baseline"] = cpu_baseline(args.n_embd, a.ctx_len)
         print(json.dumps(out))
     if dist.is_initialized():

@@ -8,7 +8,7 @@ cat $OUT/${TAG}_wkv7_ab.jsonl
 : > $OUT/${TAG}_step_ab.txt
 for rep in 1 2; do
   for v in $VARS; do
-    VRWKV_BWD_VARIANT=$v python bench.py --steps $STEPS --warmup 3 --no-cpu-baseline --no-grad-cp-companion 2>/dev/null | python -c "
+    VRWKV_BWD_VARIANT=$v python bench.py --full --steps $STEPS --warmup 3 --no-cpu-baseline --no-grad-cp-companion 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -4,7 +4,7 @@ TAG=${1:-r5}; CASES=$2; REPS=${3:-2}; O=gpurun_out; : > $O/${TAG}_step_libs_ab.t
 for rep in $(seq $REPS); do
   for c in $CASES; do
     lib=${c%%:*}; v=${c##*:}
-    VRWKV_HIP_LIB=benchmarks/_alt/lib_$lib.so VRWKV_BWD_VARIANT=$v python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-grad-cp-companion 2>/dev/null | python -c "
+    VRWKV_HIP_LIB=benchmarks/_alt/lib_$lib.so VRWKV_BWD_VARIANT=$v python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-grad-cp-companion 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

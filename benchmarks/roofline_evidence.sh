@@ -5,7 +5,7 @@ TAG=${1:-r3}; R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O
 git -C $R rev-parse HEAD > $O/commit.txt 2>/dev/null || echo "snapshot without .git (gpurun)" > $O/commit.txt
 rocm-smi --showclocks --showpower --showtemp > $O/smi_before.txt 2>&1
 cd /tmp; export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/step -o step -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-grad-cp-companion > $O/bench_under_rocprof.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/step -o step -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-grad-cp-companion > $O/bench_under_rocprof.log 2>&1
 cd $R
 rocm-smi --showclocks --showpower --showtemp > $O/smi_after.txt 2>&1
 grep '^{"metric"' $O/bench_under_rocprof.log | tail -1 > $O/bench_under_rocprof.json

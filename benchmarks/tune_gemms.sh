@@ -6,5 +6,5 @@ MB=${1:-16}; OUT=$PWD/gpurun_out/tunableop_mb${MB}
 export PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=1 PYTORCH_TUNABLEOP_FILENAME=$OUT.csv
 export PYTORCH_TUNABLEOP_MAX_TUNING_DURATION_MS=20 PYTORCH_TUNABLEOP_MAX_WARMUP_DURATION_MS=5
 mkdir -p gpurun_out
-python bench.py --steps 2 --warmup 1 --no-cpu-baseline --micro-bsz $MB --gemm-tuning 0
+python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --micro-bsz $MB --gemm-tuning 0
 ls -la ${OUT}*.csv    # PyTorch appends the device ordinal: copy ${OUT}0.csv to visualrwkv_amd/tuning/
