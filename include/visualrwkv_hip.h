@@ -135,6 +135,21 @@ int vrwkv_ce_fwd_bf16(long nrows, int V, const void* logits, const long* labels,
 int vrwkv_ce_bwd_bf16(long nrows, int V, const void* logits, const long* labels, const float* row_w, const float* row_max,
                       const float* row_lse, const int* row_argmax, float l2_factor, void* dlogits, void* stream);
 
+/* The head's backward on labelled rows only (visualrwkv_amd/fused.py _HeadCE).  A row whose row_w is 0 has one nonzero logit gradient,
+ * c = bf16(row_max * l2_factor) at its arg-max; only the other rows go through the dense backward.
+ * ce_bwd_rows: ce_bwd's rows idx[r] (int64) written as the compact (nrows, V) dlogits; idx[r] < 0 gives a row of zeros.
+ * head_dx: dx (nrows, C) bf16; pos[i] >= 0 copies row pos[i] of dxc, pos[i] == -1 writes c_i * W[argmax_i, :] (W (V, C) bf16, one
+ * rounding), pos[i] < -1 writes zeros (dxc may be NULL when no pos[i] >= 0).  C % 8 == 0.
+ * l2wrap_wgrad: dW[v, :] += sum c_p x[srow[p], :] over the n rows srow (int64, sorted by argmax, stable) with argmax v, in place on the
+ * bf16 dW (V, C); deterministic (fixed summation order, no atomics); ws: l2wrap_wgrad_ws_floats(n, C) floats. */
+int vrwkv_ce_bwd_rows_bf16(long nrows, int V, const void* logits, const long* labels, const float* row_w, const float* row_max,
+                           const float* row_lse, const int* row_argmax, float l2_factor, const long* idx, void* dlogits, void* stream);
+int vrwkv_head_dx_bf16(long nrows, int C, const long* pos, const void* dxc, const void* W, const float* row_max, const int* row_argmax,
+                       float l2_factor, void* dx, void* stream);
+long vrwkv_l2wrap_wgrad_ws_floats(long n, int C);
+int vrwkv_l2wrap_wgrad_bf16(long n, int C, const long* srow, const void* x, const float* row_max, const int* row_argmax, float l2_factor,
+                            void* dW, float* ws, void* stream);
+
 /* WKV7 forward from / to an explicit state, for inference and stateful prefill (no counterpart in the reference, whose
  * forward always starts from S = 0 and always writes its training checkpoints -- cuda/wkv7_cuda.cu:15,44-50).
  * s0: optional (B,H,64,64) f32 initial state S[i][j] (i = value row, j = key column; NULL = zeros);

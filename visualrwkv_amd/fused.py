@@ -799,6 +799,161 @@ def ce_supported(logits):
     return logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 3 and logits.shape[-1] % 8 == 0
 
 
+# Head + loss as one node whose backward runs the dense part on the labelled rows only (DESIGN.md "The head's backward on labelled rows").
+# A row without a label has one nonzero logit gradient (L2Wrap's c = bf16(max * 1e-4/(B*T)) at its arg-max): its input gradient is c W[arg]
+# and its weight gradient c x added to W's row arg, both from csrc/loss_fused.hip.  The two head GEMMs and the CE backward run over the
+# labelled rows, padded to HEAD_ROW_ALIGN (one tuned shape per labelled count of the batch).  0 = linear + _FusedCE (dense over every row).
+HEAD_COMPACT = os.environ.get("VRWKV_HEAD_COMPACT", "1") != "0"
+HEAD_ROW_ALIGN = 256
+# above this labelled fraction the dense backward is used: the compact path saves GEMM rows in proportion to the unlabelled share and
+# costs a few hundred us of its own (gather, sort, dx assembly, sparse weight gradient); the two meet at 0.95 at the bench shape
+# (profiles/r7_head_compact_micro.jsonl)
+HEAD_COMPACT_MAX_FRACTION = 0.9
+
+
+class HeadPlan:
+    """The labelled rows of one batch, formed at the start of training_step from the labels alone: the shifted labels and per-row loss
+    weights of _FusedCE, and the count of labelled rows copied to pinned host memory behind an event -- by the head's backward the copy has
+    long landed, so reading it waits for nothing (no device-wide synchronisation in the step).  Rows are those of the hidden state left-padded
+    by `pad` rows per sample (RWKV.forward_features): pad rows carry no label and get no gradient.  Nothing is cached across batches."""
+
+    def __init__(self, targets, pad, ignore_index=-100):
+        B, T = targets.shape
+        dev = targets.device
+        labels = torch.full((B, T), ignore_index, dtype=torch.long, device=dev)
+        labels[:, :-1] = targets[:, 1:]                       # row (b,t) predicts token t+1; the last row has no target
+        labels = torch.where(labels == ignore_index, torch.full_like(labels, -100), labels)
+        valid = (labels >= 0).sum(1).clamp(min=1)
+        self.w = ((labels >= 0).float() / (valid.float().unsqueeze(1) * B)).view(B * T)      # _FusedCE's d loss / d row_loss
+        self.B, self.T, self.pad = B, T, pad
+        Tp = T + pad
+        lab_p = torch.full((B, Tp), -100, dtype=torch.long, device=dev)
+        lab_p[:, pad:] = labels
+        self.labels = lab_p.view(B * Tp)                      # padded layout: what the kernels index
+        mask = self.labels >= 0
+        count = mask.sum()
+        self.n_host = torch.empty(1, dtype=torch.long, pin_memory=True)
+        self.n_host.copy_(count.view(1), non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record(torch.cuda.current_stream(dev))
+        self.count = count
+        self.order = torch.argsort(~mask, stable=True)         # labelled rows first, ascending
+        real = torch.zeros(B, Tp, dtype=torch.bool, device=dev)
+        real[:, pad:] = True
+        # pos: compact slot of a labelled row, -1 for a row without a label, -2 for a pad row
+        self.pos = torch.where(mask, torch.cumsum(mask, 0) - 1, torch.where(real.view(-1), -1, -2))
+        self._n = None
+
+    def n_labelled(self):
+        if self._n is None:
+            self.event.synchronize()
+            self._n = int(self.n_host[0])
+        return self._n
+
+    def idx(self, nrows):
+        """Source row of each of the nrows compact rows: the labelled rows in order, then -1."""
+        n = self.order.numel()
+        idx = torch.full((nrows,), -1, dtype=torch.long, device=self.order.device)
+        k = min(nrows, n)
+        idx[:k] = torch.where(torch.arange(k, device=idx.device) < self.count, self.order[:k], -1)
+        return idx
+
+
+def head_loss_supported(head, labels, x=None):
+    """May training_step take head + loss through _HeadCE?  `x`: the hidden state, once it exists."""
+    w = head.weight
+    return (HEAD_COMPACT and torch.is_grad_enabled() and labels.is_cuda and w.is_cuda and w.dtype == torch.bfloat16 and head.bias is None
+            and w.dim() == 2 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0
+            and (x is None or (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3 and x.shape[-1] == w.shape[1])))
+
+
+class _HeadCE(torch.autograd.Function):
+    """loss_from_logits(unpad(linear(head, x))) for the left-padded hidden state x (B, T+pad, C) -- the same forward GEMM over the same
+    rows and the same CE kernel, so the loss is bit-identical.  Backward: ce_bwd on the labelled rows into a compact gradient, the input
+    gradient of those rows from one library GEMM, c W[arg] for the others (head_dx), the weight gradient of the labelled rows from one
+    library GEMM into the ZeRO-1 slot (_weight_grad) plus the sparse L2Wrap rows (l2wrap_wgrad).  The GEMMs run one after the other.
+    Above HEAD_COMPACT_MAX_FRACTION labelled rows the backward is the dense one of linear + _FusedCE, over every row, with the same
+    kernels and GEMM shapes."""
+
+    @staticmethod
+    def forward(ctx, x, w, plan):
+        x = x.contiguous()
+        _chk(x, w)
+        B, Tp, C = x.shape
+        if B != plan.B or Tp != plan.T + plan.pad:
+            raise ValueError(f"head_loss: hidden state {tuple(x.shape)} does not match the plan ({plan.B}, {plan.T} + {plan.pad})")
+        logits = F.linear(x, w)
+        V = logits.shape[-1]
+        n = B * Tp
+        dev = x.device
+        row_loss, row_max, row_lse = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+        row_arg = torch.empty(n, dtype=torch.int32, device=dev)
+        rc = hip_lib.load().vrwkv_ce_fwd_bf16(n, V, logits.data_ptr(), plan.labels.data_ptr(), row_loss.data_ptr(),
+                                              row_max.data_ptr(), row_lse.data_ptr(), row_arg.data_ptr(), _stream(logits))
+        hip_lib.check(rc, "vrwkv_ce_fwd_bf16")
+        ctx.save_for_backward(x, w, logits, row_max, row_lse, row_arg)
+        ctx.plan = plan
+        ctx.wparam = w if hasattr(w, "_vrwkv_flat_grad") else None
+        return (row_loss.view(B, Tp)[:, plan.pad:].reshape(-1) * plan.w).sum().to(logits.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, logits, row_max, row_lse, row_arg = ctx.saved_tensors
+        plan = ctx.plan
+        B, Tp, C = x.shape
+        V = w.shape[0]
+        N, n_real = B * Tp, B * plan.T
+        dev = x.device
+        lib = hip_lib.load()
+        st = _stream(x)
+        row_w = torch.zeros(B, Tp, dtype=torch.float32, device=dev)
+        row_w[:, plan.pad:] = (plan.w * g.float()).view(B, plan.T)      # _FusedCE's row_w on the real rows, 0 on the pad rows
+        row_w = row_w.view(N)
+        l2f = 1e-4 / n_real
+        x2 = x.view(N, C)
+        n_lab = plan.n_labelled()
+        compact = n_lab <= HEAD_COMPACT_MAX_FRACTION * n_real
+        if compact:
+            nrows = -(-n_lab // HEAD_ROW_ALIGN) * HEAD_ROW_ALIGN
+            idx = plan.idx(nrows)
+        else:                                                            # every real row dense: linear + _FusedCE's backward
+            nrows = N
+            idx = torch.where(plan.pos >= -1, torch.arange(N, device=dev), -1)
+        dlog = torch.empty(nrows, V, dtype=torch.bfloat16, device=dev)
+        if nrows:
+            rc = lib.vrwkv_ce_bwd_rows_bf16(nrows, V, logits.data_ptr(), plan.labels.data_ptr(), row_w.data_ptr(), row_max.data_ptr(),
+                                            row_lse.data_ptr(), row_arg.data_ptr(), l2f, idx.data_ptr(), dlog.data_ptr(), st)
+            hip_lib.check(rc, "vrwkv_ce_bwd_rows_bf16")
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dxc = F.linear(dlog, transpose2d(w)) if nrows else torch.empty(0, C, dtype=x.dtype, device=dev)
+            if compact:
+                dx = torch.empty(N, C, dtype=x.dtype, device=dev)
+                rc = lib.vrwkv_head_dx_bf16(N, C, plan.pos.data_ptr(), dxc.data_ptr(), w.data_ptr(), row_max.data_ptr(), row_arg.data_ptr(),
+                                            l2f, dx.data_ptr(), st)
+                hip_lib.check(rc, "vrwkv_head_dx_bf16")
+            else:
+                dx = dxc
+            dx = dx.view(B, Tp, C)
+        if ctx.needs_input_grad[1]:
+            xl = x2.index_select(0, idx.clamp(min=0)) if compact else x2      # compact padding rows: any row (its gradient row is 0)
+            dw = _weight_grad(ctx.wparam, dlog, xl)
+            n_u = n_real - n_lab
+            if compact and n_u > 0:
+                key = torch.where(plan.pos == -1, row_arg.long(), V)
+                srow = torch.sort(key, stable=True).indices[:n_u].contiguous()
+                ws = torch.empty(lib.vrwkv_l2wrap_wgrad_ws_floats(n_u, C), dtype=torch.float32, device=dev)
+                rc = lib.vrwkv_l2wrap_wgrad_bf16(n_u, C, srow.data_ptr(), x2.data_ptr(), row_max.data_ptr(), row_arg.data_ptr(), l2f,
+                                                 dw.data_ptr(), ws.data_ptr(), st)
+                hip_lib.check(rc, "vrwkv_l2wrap_wgrad_bf16")
+        return dx, dw, None
+
+
+def head_loss(head, x, plan):
+    """training_step's loss from the left-padded hidden state x = RWKV.forward_features(...)[0]: _HeadCE (see there)."""
+    return _HeadCE.apply(x, head.weight, plan)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # RWKV-6 glue (BASELINE config 4; VisualRWKV-v6/v6.0/src/model.py:146-194, 213-226)
 # ---------------------------------------------------------------------------------------------------------------

@@ -35,6 +35,10 @@ PROTOTYPES = {
     "vrwkv_mix_bwd_ln_bf16": (_c_int, [_c_long, _c_int, _c_int, _c_int] + [_c_void_p] * 12),
     "vrwkv_ce_fwd_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 7),
     "vrwkv_ce_bwd_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 6 + [_c_float] + [_c_void_p] * 2),
+    "vrwkv_ce_bwd_rows_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 6 + [_c_float] + [_c_void_p] * 3),
+    "vrwkv_head_dx_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 5 + [_c_float] + [_c_void_p] * 2),
+    "vrwkv_l2wrap_wgrad_ws_floats": (_c_long, [_c_long, _c_int]),
+    "vrwkv_l2wrap_wgrad_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 4 + [_c_float] + [_c_void_p] * 3),
     "vrwkv_gemv_multi_bf16": (_c_int, [_c_int, _c_int] + [_c_void_p] * 8),
     "vrwkv_decode_ln_mix_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 3 + [_c_float] + [_c_void_p] * 4),
     "vrwkv_decode_tmix_head_bf16": (_c_int, [_c_int] * 2 + [_c_void_p] * 15 + [_c_float] + [_c_void_p] * 5),

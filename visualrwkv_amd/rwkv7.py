@@ -311,7 +311,10 @@ class RWKV(nn.Module):
                 x, v_first = block(x, v_first)
         return self.ln_out(x), num_tokens_to_pad
 
-    def forward(self, x):
+    def forward(self, x, hidden_only=False):
+        """Logits (B, T, V); hidden_only: forward_features(x) instead (through the module call, so that forward pre-hooks run)."""
+        if hidden_only:
+            return self.forward_features(x)
         x, num_tokens_to_pad = self.forward_features(x)
         if x.is_cuda and getattr(self.args, "fused", False):
             from . import fused

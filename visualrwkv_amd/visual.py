@@ -172,7 +172,22 @@ class VisualRWKV(nn.Module):
         return L2Wrap.apply(loss, logits)
 
     def training_step(self, batch, batch_idx=0):
-        logits, targets = self(batch)
+        logits = None
+        if getattr(self.args, "fused", False):
+            from . import fused
+            from .rwkv7 import CHUNK_LEN
+            targets = batch["labels"]
+            if fused.head_loss_supported(self.rwkv.head, targets):
+                # head + loss as one node (backward dense on the labelled rows only); the labelled rows are counted before the forward is
+                # issued, so that the head's backward finds the count in pinned memory without waiting
+                plan = fused.HeadPlan(targets, (CHUNK_LEN - targets.shape[1] % CHUNK_LEN) % CHUNK_LEN, IGNORE_INDEX)
+                x, _ = self.preparing_embedding(batch)
+                h, num_tokens_to_pad = self.rwkv(x, hidden_only=True)
+                if num_tokens_to_pad == plan.pad and fused.head_loss_supported(self.rwkv.head, targets, h):
+                    return fused.head_loss(self.rwkv.head, h, plan)
+                logits = self.rwkv.unpad(fused.linear(self.rwkv.head, h), num_tokens_to_pad)     # RWKV.forward's head
+        if logits is None:
+            logits, targets = self(batch)
         if getattr(self.args, "fused", False):
             from . import fused
             if fused.ce_supported(logits):
