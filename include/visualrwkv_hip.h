@@ -72,6 +72,21 @@ int vrwkv_wkv7_backward_segments_bf16(int B, int T, int H, int nseg, const void*
                                       const float* sa, const float* ds_in, float* ds_out,
                                       void* dw, void* dq, void* dk, void* dv, void* dz, void* da, void* stream);
 
+/* The training backward with a carried state (no counterpart in the reference: its WindBackstepping has no state argument).  The math is
+ * that of oracle/wkv7_oracle.py::wkv7_naive(w, q, k, v, z, a, state0) -> (y, state_T) differentiated: the tensors of
+ * vrwkv_wkv7_backward_bf16, with `s` / `sa` as vrwkv_wkv7_forward_state_bf16 wrote them (s_ckpt, sa) from s0, plus
+ *   s0       (B,H,64,64) f32, [value row i][key column j]: the state that forward started from (NULL = zeros).  The checkpoints begin at the
+ *            END of chunk 0, so dq, dz and dw of the first 16 tokens need it;
+ *   ds_final (B,H,64,64) f32, same order: dL/d(state after the last token) (NULL = zeros);
+ *   ds0      (B,H,64,64) f32: receives dL/d(s0) (NULL = not wanted).
+ * Same argument checks, kernel choice (5 / 8 / 9, vrwkv_wkv7_set_backward_variant) and batch slices as vrwkv_wkv7_backward_bf16; with the
+ * three pointers NULL the six gradients are bit-identical to that entry's.  Variants 8 / 9 run the STATE instantiation of csrc/wkv7_bwd_v8.h,
+ * variant 5 the sequence-parallel kernel of csrc/wkv7_bwd_v5.h with one segment per head. */
+int vrwkv_wkv7_backward_state_bf16(int B, int T, int H, const void* w, const void* q, const void* k, const void* v,
+                                   const void* z, const void* a, const void* dy, const float* s, const float* sa,
+                                   const float* s0, const float* ds_final, float* ds0,
+                                   void* dw, void* dq, void* dk, void* dv, void* dz, void* da, void* stream);
+
 /* WKV6 (BASELINE config 4): replaces cuda_forward / cuda_backward of VisualRWKV-v6/v6.0/cuda/wkv6_cuda.cu:229-242 as bound
  * by cuda/wkv6_op.cpp:8-13 (forward(B,T,C,H,r,k,v,w,u,y), backward(B,T,C,H,r,k,v,w,u,gy,gr,gk,gv,gw,gu)).
  * r,k,v,y,gy,gr,gk,gv,gw: (B,T,C) bf16; ew: (B,T,C) f32 = -exp(w_raw) as WKV_6.forward computes it (src/model.py:62);
@@ -217,13 +232,13 @@ int vrwkv_wkv7_set_backward_variant(int variant);
 /* Test hook: the tensor size (bytes of the fp32 `sa`, B*T*H*64*4) from which vrwkv_wkv7_backward_bf16 cuts a launch into batch slices (the default
  * kernel forms 32-bit byte offsets inside a tensor); 0 = the default, 4 GiB.  Results do not depend on it. */
 int vrwkv_wkv7_set_backward_slice_limit(unsigned long long bytes);
-/* The kernel generation the LAST vrwkv_wkv7_forward_bf16 (backward == 0) / vrwkv_wkv7_backward_bf16 (backward != 0) launch of this
+/* The kernel generation the LAST vrwkv_wkv7_forward_bf16 (backward == 0) / vrwkv_wkv7_backward_bf16 or vrwkv_wkv7_backward_state_bf16 (backward != 0) launch of this
  * process resolved to, in the numbering above (forward: 7 = wkv7_fwd_v4.h, 6 = two workgroups per head, 4 = wkv7_fwd_v3.h; 0 = none yet);
  * vrwkv_wkv7_forward_state_bf16 records into the forward slot as well.  Lets a single-threaded parity test assert WHICH kernel the default
  * dispatch chose for its shape. */
 int vrwkv_wkv7_last_variant(int backward);
 /* Which kernel generation a launch of shape (B,T,H) resolves to under the current override, WITHOUT launching: kind 0 = vrwkv_wkv7_forward_bf16,
- * 1 = vrwkv_wkv7_backward_bf16, 2 = vrwkv_wkv7_forward_state_bf16 (same rule as kind 0; its A/B overrides 1..5 all mean 4).  A pure function of
+ * 1 = vrwkv_wkv7_backward_bf16, 2 = vrwkv_wkv7_forward_state_bf16 (same rule as kind 0; its A/B overrides 1..5 all mean 4), 3 = vrwkv_wkv7_backward_state_bf16 (same rule as kind 1).  A pure function of
  * its arguments and the override: unlike vrwkv_wkv7_last_variant it does not depend on which thread launched last (the reference calls the op
  * from the Python thread and from autograd's backward thread).  A bad shape or kind gives VRWKV_EINVAL (< 0). */
 int vrwkv_wkv7_resolve_variant(int kind, int B, int T, int H);

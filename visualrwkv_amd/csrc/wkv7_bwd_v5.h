@@ -200,6 +200,15 @@ DEVFN void dma_state(float* img, const float* s_chunk, int k0, int k1, int lane)
         for (int k = k0; k < k1; ++k) *reinterpret_cast<float4*>(img + 4 * k * N + 4 * lane) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
+// The same image from a state in [i][j] order (BwdArgs::s0: the state a stateful forward started from): the transpose goes through
+// registers, four strided loads per 16-byte slot.  Once per launch and head.
+DEVFN void fill_state_T(float* img, const float* s0, int k0, int k1, int lane) {
+    for (int k = k0; k < k1; ++k) {
+        const int row = 4 * k + (lane >> 4), i0 = ((lane & 15) ^ (row & 15)) << 2;
+        *reinterpret_cast<float4*>(img + 4 * k * N + 4 * lane) =
+            make_float4(s0[(i0 + 0) * N + row], s0[(i0 + 1) * N + row], s0[(i0 + 2) * N + row], s0[(i0 + 3) * N + row]);
+    }
+}
 
 // U^T V on the f32 matrix core with two independent accumulation chains (dependent f32 MFMAs cost 40 cycles each)
 DEVFN f32x4 regmm_f32x2(f32x4 u, f32x4 v) {
@@ -295,7 +304,8 @@ DEVFN void tiles_op(const f32x4* tl, bf16x8* oh, bf16x8* ol) {
 // MODE bit 7 (128): priorities by segment -- in segment 1 the producers drop to 0 and the consumers rise to 1 (the producers
 // have ~1.2k cycles of slack per chunk there and the consumers none); everywhere else the producers stay above the consumers.
 // TPAR: sequence-parallel launch: blockIdx.x = (b*H + h) * nseg + seg, chunks [c_lo, c_hi),
-// dL/dS enters as ds_in[b,h,seg] and leaves as ds_out[b,h,seg] (both [i][j] fp32).  A launch that only asks for ds_out
+// dL/dS enters as ds_in[b,h,seg] and leaves as ds_out[b,h,seg] (both [i][j] fp32); with s0 set (nseg = 1: the training op with a carried
+// state, vrwkv_wkv7_backward_state_bf16) chunk 0 continues from s0[b,h] instead of zeros.  A launch that only asks for ds_out
 // (ds_in == null: the first pass of the sequence-parallel backward, whose gradients are discarded) runs LITE: only what
 // propagates dL/dS is computed -- no S0 images, no score gradients, no dV, no j-split output products, no tail, no stores.
 template <bool PROF, int MODE = 0, bool TPAR = false>
@@ -313,7 +323,7 @@ __global__ __launch_bounds__(512) void bwd_kernel_v5(BwdArgs p) {
     const int c_lo = TPAR ? (int)((long)nchunk * seg / nseg) : 0, c_hi = TPAR ? (int)((long)nchunk * (seg + 1) / nseg) : nchunk;
     const size_t head_base = ((size_t)(bh / H) * T * H + (bh % H)) * N;
     const float* sbase = p.s + (size_t)bh * nchunk * N * N;
-    const bool lite = TPAR && p.ds_out != nullptr && p.ds_in == nullptr;        // wave-uniform; constant false without TPAR
+    const bool lite = TPAR && p.ds_out != nullptr && p.ds_in == nullptr && !p.want_grads;        // wave-uniform; constant false without TPAR
     WKV_STAMP_DECL
     const unsigned long long rt0_ = PROF ? realtime64_() : 0ull;       // constant-rate (100 MHz) counter: cycles / time = shader clock
 
@@ -336,13 +346,17 @@ __global__ __launch_bounds__(512) void bwd_kernel_v5(BwdArgs p) {
         {   // prologue: the last chunk, completely
             KeepB keep;
             BufV5& B = lds.b[(c_hi - 1) & 1];
-            if (!lite) dma_state(B.s0, c_hi - 1 > 0 ? sbase + (size_t)(c_hi - 2) * N * N : nullptr, 4 * pw, 4 * pw + 4, lane);   // S0 of chunk c is s[c-1]
+            // S0 of chunk 0 with a carried state (TPAR, BwdArgs::s0): the state the forward started from instead of zeros, here and at the two requests below
+            if (TPAR && !lite && c_hi - 1 == 0 && p.s0) fill_state_T(B.s0, p.s0 + (size_t)bh * N * N, 4 * pw, 4 * pw + 4, lane);
+            else if (!lite) dma_state(B.s0, c_hi - 1 > 0 ? sbase + (size_t)(c_hi - 2) * N * N : nullptr, 4 * pw, 4 * pw + 4, lane);   // S0 of chunk c is s[c-1]
             prep_a(B, raw, c16, 16 * pw + 4 * g, la, keep);
             prep_b(B, raw, la, keep);
             if (c_hi - 1 > c_lo) fetch(raw, c_hi - 2);
             block_sync_lds();
             if (!lite || pw < 2) scores<(MODE & 2) != 0>(B, pw, c16, g, la);       // lite: only T and M_qa are used
-            if (!lite && pw > 0 && c_hi - 1 > c_lo)
+            if (TPAR && !lite && pw > 0 && c_hi - 1 > c_lo && c_hi - 2 == 0 && p.s0)
+                fill_state_T(lds.b[(c_hi - 2) & 1].s0, p.s0 + (size_t)bh * N * N, pw == 1 ? 0 : pw == 2 ? 5 : 10, pw == 1 ? 5 : pw == 2 ? 10 : 16, lane);
+            else if (!lite && pw > 0 && c_hi - 1 > c_lo)
                 dma_state(lds.b[(c_hi - 2) & 1].s0, c_hi - 2 > 0 ? sbase + (size_t)(c_hi - 3) * N * N : nullptr, pw == 1 ? 0 : pw == 2 ? 5 : 10, pw == 1 ? 5 : pw == 2 ? 10 : 16, lane);
             block_sync_lds();
         }
@@ -371,7 +385,9 @@ __global__ __launch_bounds__(512) void bwd_kernel_v5(BwdArgs p) {
             block_sync_lds();                           // Y: dM(c) ready, all images of c-1 written
             WKV_STAMP(5)
             if (more && (!lite || pw < 2)) scores<(MODE & 2) != 0>(Bn, pw, c16, g, la);
-            if (!lite && pw > 0 && c - 1 > c_lo)                 // S0 of chunk c-2 = s[c-3] into the buffer the consumers have just left
+            if (TPAR && !lite && pw > 0 && c - 1 > c_lo && c - 2 == 0 && p.s0)
+                fill_state_T(lds.b[c & 1].s0, p.s0 + (size_t)bh * N * N, pw == 1 ? 0 : pw == 2 ? 5 : 10, pw == 1 ? 5 : pw == 2 ? 10 : 16, lane);
+            else if (!lite && pw > 0 && c - 1 > c_lo)                 // S0 of chunk c-2 = s[c-3] into the buffer the consumers have just left
                 dma_state(lds.b[c & 1].s0, c - 2 > 0 ? sbase + (size_t)(c - 3) * N * N : nullptr, pw == 1 ? 0 : pw == 2 ? 5 : 10, pw == 1 ? 5 : pw == 2 ? 10 : 16, lane);
             WKV_STAMP(6)
             block_sync_lds();                           // Z

@@ -187,7 +187,16 @@ DEVFN void tail8(LdsV8& lds, int par, const TailQ& tr, const BwdArgs& p, size_t 
 // waves 1-3 at the start of the next step, where they delayed the i-split's chain by 1.6-1.8k cycles.  The P waves prepare the
 // images BEFORE their tail for that (the queue entry of the prepare is assigned after the tail has consumed the old one).
 // Wave priorities: I 0, J 0, P 1 (profiles/r2_wkv7_ab_priority.jsonl, r5_wkv7_jtail_priorities.jsonl).
-template <bool PROF, bool AHEAD = false>
+// STATE (vrwkv_wkv7_backward_state_bf16): the training op with a carried state.  dL/dS has ONE home here, so three local changes suffice:
+//   * the I waves start their accumulators from ds_in[b,h] (dL/dS after the last token; null = 0) and store them to ds_out[b,h] after chunk 0
+//     (null = not wanted): 4 x 16-byte loads / stores per lane, rows of 64 floats contiguous over the 16 lanes of a group's tiles;
+//   * the hand-over image of the first active step is formed from those accumulators like every other, so the J waves' dU of the last chunk is
+//     the seeded one; what they lack is S_L of that chunk for the decay-gradient diagonal (zero operands stand in for it when dL/dS starts at 0).
+//     It is the last checkpoint s[nchunk-1] ([j][i], the order of their S0 tiles): 4 x 16-byte loads per lane before the loop, split like an S0;
+//   * S0 of chunk 0 is s0[b,h] (the state the forward started from; null = 0) instead of zeros: the P waves fill the image through registers
+//     (the checkpoints hold S^T, states are [i][j]: LDS-DMA cannot transpose) in the ragged step that zero-fills it otherwise.
+// No new role, no new LDS image, no change to a steady-state (FULL) step.  With STATE off every `if (STATE ...)` folds away.
+template <bool PROF, bool AHEAD = false, bool STATE = false>
 __global__ __launch_bounds__(768) void bwd_kernel_v8(BwdArgs p) {
     LdsV8& lds = *reinterpret_cast<LdsV8*>(dyn_lds());
     const int T = p.T, H = p.H;
@@ -265,7 +274,8 @@ __global__ __launch_bounds__(768) void bwd_kernel_v8(BwdArgs p) {
                 if (FULL) {
                     const float* sc = sbase + (size_t)(cd - 1) * N * N;
                     if (w == 1) s0_lean<0>(lds, sc, ll); else if (w == 2) s0_lean<1>(lds, sc, ll); else if (w == 3) s0_lean<2>(lds, sc, ll);
-                } else if (cd >= 0 && cd <= nchunk - 1) dma_state(lds.s0, cd > 0 ? sbase + (size_t)(cd - 1) * N * N : nullptr, k0, k1, lane);
+                } else if (STATE && cd == 0 && p.s0) fill_state_T(lds.s0, p.s0 + (size_t)bh * N * N, k0, k1, lane);
+                else if (cd >= 0 && cd <= nchunk - 1) dma_state(lds.s0, cd > 0 ? sbase + (size_t)(cd - 1) * N * N : nullptr, k0, k1, lane);
             }
             if (FULL || (ct >= 0 && ct <= nchunk - 1)) tail8(lds, ct & 1, qt, p, head_base + (size_t)ct * L * ts, lane_boff, c16, w, g, la);
             WKV_STAMP(0)
@@ -308,6 +318,14 @@ __global__ __launch_bounds__(768) void bwd_kernel_v8(BwdArgs p) {
         f32x4 dS1[4];                                       // dS1[jb][r] = dS[i = 16w+c16][j = tix(jb, 4g+r)]: the only copy of dL/dS
 #pragma unroll
         for (int x = 0; x < 4; ++x) dS1[x] = zero4();
+        if (STATE && p.ds_in) {
+            const float* di = p.ds_in + (size_t)bh * N * N + (size_t)(16 * w + c16) * N;
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                const float4 t = *reinterpret_cast<const float4*>(di + tix(x, 4 * g));
+                dS1[x][0] = t.x; dS1[x][1] = t.y; dS1[x][2] = t.z; dS1[x][3] = t.w;
+            }
+        }
         unsigned n_sc = 0, n_t = 0;
         const int img_row = img_off(16 * w + c16, 8 * g);   // this lane's 16-byte piece of the dS image, k block 0 (+ 32 columns: block 1)
         const int img_row1 = img_off(16 * w + c16, 32 + 8 * g);
@@ -420,6 +438,11 @@ __global__ __launch_bounds__(768) void bwd_kernel_v8(BwdArgs p) {
             block_sync_lds();
             WKV_STAMP(3)
         }
+        if (STATE && p.ds_out) {                            // dL/dS before the first token
+            float* dout = p.ds_out + (size_t)bh * N * N + (size_t)(16 * w + c16) * N;
+#pragma unroll
+            for (int x = 0; x < 4; ++x) *reinterpret_cast<float4*>(dout + tix(x, 4 * g)) = make_float4(dS1[x][0], dS1[x][1], dS1[x][2], dS1[x][3]);
+        }
         WKV_STAMP_FLUSH(64 * VRWKV_PROF_WAVE, 0, 5)
         if (PROF && blockIdx.x == 0 && tid == 64 * VRWKV_PROF_WAVE) { p.dbg[15] = realtime64_() - rt0_; p.dbg[18] = tacc_[5]; p.dbg[19] = tacc_[6]; }   // i-split: dSA + dR | dV
         return;
@@ -435,6 +458,16 @@ __global__ __launch_bounds__(768) void bwd_kernel_v8(BwdArgs p) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) tro[kb][h] = img_off(32 * kb + 8 * g + 4 * h + (c16 >> 2), 16 * w + 4 * (c16 & 3));
     bf16x8 s0h_p[2] = {mk8(0u, 0u, 0u, 0u), mk8(0u, 0u, 0u, 0u)}, s0l_p[2] = {mk8(0u, 0u, 0u, 0u), mk8(0u, 0u, 0u, 0u)};   // S0 operands of the previous step = S_L of this one
+    if (STATE && p.ds_in) {                             // S_L of the last chunk = the state after the last token: its dL/dS is not zero here
+        const float* sp = sbase + (size_t)(nchunk - 1) * N * N + (size_t)j * N;
+        f32x4 SL[4];
+#pragma unroll
+        for (int ib = 0; ib < 4; ++ib) {
+            const float4 x = *reinterpret_cast<const float4*>(sp + tix(ib, 4 * g));
+            SL[ib][0] = x.x; SL[ib][1] = x.y; SL[ib][2] = x.z; SL[ib][3] = x.w;
+        }
+        tiles_op(SL, s0h_p, s0l_p);
+    }
     unsigned n_dm = 0;
     for (int n = 0; n < nsteps; ++n) {
         const int cj = nchunk + 1 - n;

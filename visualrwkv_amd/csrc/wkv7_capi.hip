@@ -88,9 +88,9 @@ int vrwkv_wkv7_set_backward_slice_limit(unsigned long long bytes) {
 int vrwkv_wkv7_last_variant(int backward) { return backward ? g_last_bwd.load() : g_last_fwd.load(); }
 
 int vrwkv_wkv7_resolve_variant(int kind, int B, int T, int H) {
-    if (check_common(B, T, H) != VRWKV_OK || kind < 0 || kind > 2) return VRWKV_EINVAL;
+    if (check_common(B, T, H) != VRWKV_OK || kind < 0 || kind > 3) return VRWKV_EINVAL;
     const long heads = (long)B * H;
-    if (kind == 1) return resolve_bwd(heads, g_bwd_variant.load());
+    if (kind == 1 || kind == 3) return resolve_bwd(heads, g_bwd_variant.load());
     return resolve_fwd(heads, g_fwd_variant.load(), kind == 2);
 }
 
@@ -180,6 +180,52 @@ int vrwkv_wkv7_backward_bf16(int B, int T, int H, const void* w, const void* q, 
             rc2 = launch_lds(&wkv7v8::bwd_kernel_v8<false>, grid, dim3(768), sizeof(wkv7v8::LdsV8), st, p);
         else                 // second-generation schedule, 64-bit addressing (wkv7_bwd_v5.h)
             rc2 = launch_lds(&wkv7v5::bwd_kernel_v5<false, BWD_V5_MODE>, grid, dim3(512), sizeof(wkv7v5::LdsV5), st, p);
+        if (rc2) return rc2;
+    }
+    return VRWKV_OK;
+}
+
+int vrwkv_wkv7_backward_state_bf16(int B, int T, int H, const void* w, const void* q, const void* k, const void* v,
+                                   const void* z, const void* a, const void* dy, const float* s, const float* sa,
+                                   const float* s0, const float* ds_final, float* ds0,
+                                   void* dw, void* dq, void* dk, void* dv, void* dz, void* da, void* stream) {
+    int rc = check_common(B, T, H);
+    if (rc) return rc;
+    if (!w || !q || !k || !v || !z || !a || !dy || !s || !sa || !dw || !dq || !dk || !dv || !dz || !da) return VRWKV_EINVAL;
+    if (misaligned(w) || misaligned(q) || misaligned(k) || misaligned(v) || misaligned(z) || misaligned(a) ||
+        misaligned(dy) || misaligned(s) || misaligned(sa) || misaligned(dw) || misaligned(dq) || misaligned(dk) ||
+        misaligned(dv) || misaligned(dz) || misaligned(da) || misaligned(s0) || misaligned(ds_final) || misaligned(ds0))
+        return VRWKV_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    // same kernel choice and the same batch slices as vrwkv_wkv7_backward_bf16; the states are per sample and are sliced with the batch
+    int var = resolve_bwd((long)B * H, g_bwd_variant.load());
+    if (var != 8 && var != 9) var = 5;
+    const unsigned long long per_sample = (unsigned long long)T * H * 64ull * 4ull, limit = g_slice_limit.load();
+    int bmax = B;
+    if (var >= 8 && (unsigned long long)B * per_sample >= limit) {
+        bmax = (int)((limit - 1) / per_sample);
+        if (bmax < 1) { var = 5; bmax = B; }
+    }
+    g_last_bwd = var;
+    const size_t act = (size_t)T * H * 64, ckpt = (size_t)H * (T / VRWKV_CHUNK_LEN) * 64 * 64, stt = (size_t)H * 64 * 64;      // elements per sample
+    for (int b0 = 0; b0 < B; b0 += bmax) {
+        const int nb = B - b0 < bmax ? B - b0 : bmax;
+        const size_t o = (size_t)b0 * act;
+        wkv7::BwdArgs p{T, H, (const uint16_t*)w + o, (const uint16_t*)q + o, (const uint16_t*)k + o, (const uint16_t*)v + o,
+                        (const uint16_t*)z + o, (const uint16_t*)a + o, (const uint16_t*)dy + o, s + (size_t)b0 * ckpt, sa + o,
+                        (uint16_t*)dw + o, (uint16_t*)dq + o, (uint16_t*)dk + o, (uint16_t*)dv + o, (uint16_t*)dz + o, (uint16_t*)da + o};
+        p.ds_in = ds_final ? ds_final + (size_t)b0 * stt : nullptr;
+        p.ds_out = ds0 ? ds0 + (size_t)b0 * stt : nullptr;
+        p.s0 = s0 ? s0 + (size_t)b0 * stt : nullptr;
+        p.want_grads = 1;
+        const dim3 grid((unsigned)((long)nb * H));
+        int rc2;
+        if (var == 9)
+            rc2 = launch_lds(&wkv7v8::bwd_kernel_v8<false, true, true>, grid, dim3(768), sizeof(wkv7v8::LdsV8), st, p);
+        else if (var == 8)
+            rc2 = launch_lds(&wkv7v8::bwd_kernel_v8<false, false, true>, grid, dim3(768), sizeof(wkv7v8::LdsV8), st, p);
+        else                 // the sequence-parallel kernel with one segment per head: it carries both state gradients already
+            rc2 = launch_lds(&wkv7v5::bwd_kernel_v5<false, BWD_V5_MODE, true>, grid, dim3(512), sizeof(wkv7v5::LdsV5), st, p);
         if (rc2) return rc2;
     }
     return VRWKV_OK;

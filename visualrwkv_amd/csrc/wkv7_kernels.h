@@ -46,6 +46,11 @@ struct BwdArgs {
     const float* ds_in = nullptr;                 // f32 (B,H,nseg,N,N), [i][j]
     float* ds_out = nullptr;
     int nseg = 1;
+    // carried state (bwd_kernel_v8<.., STATE>, bwd_kernel_v5<.., TPAR> with nseg = 1): the state the forward started from, [i][j] like ds_in
+    // (null = 0).  The checkpoints `s` begin at the END of chunk 0, so the j-split of chunk 0 (dq, dz and through them dw) takes its S0 from here.
+    const float* s0 = nullptr;                    // f32 (B,H,N,N)
+    int want_grads = 0;                           // TPAR: 1 = a launch with ds_out and no ds_in still computes the six gradients (the state op);
+                                                  // 0 = it is pass 1 of the sequence-parallel backward, whose gradients nobody reads (LITE)
 };
 
 

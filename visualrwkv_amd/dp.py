@@ -94,8 +94,10 @@ class Zero1Engine:
         names = {id(p): n for n, p in model.named_parameters()}
         late = lambda p: names.get(id(p), "").startswith(("proj.", "rwkv.emb.", "emb."))
         by_ready = [p for p in params[::-1] if not late(p)] + [p for p in params[::-1] if late(p)]
-        wd = [p for p in by_ready if len(p.squeeze().shape) >= 2]
-        nowd = [p for p in by_ready if len(p.squeeze().shape) < 2]
+        # as VisualRWKV.optimizer_groups: at least 2-D after squeeze() = weight decay, except the learnable initial WKV states (args.state_tune)
+        decays = lambda p: len(p.squeeze().shape) >= 2 and not names.get(id(p), "").endswith(".time_state")
+        wd = [p for p in by_ready if decays(p)]
+        nowd = [p for p in by_ready if not decays(p)]
         ordered = wd + nowd
         align = 8 * self.world                       # every piece 16-byte aligned in bf16
         offs, total = [], 0

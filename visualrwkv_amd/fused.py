@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from . import gemm_tuning, hip_lib
-from .wkv7 import RUN_CUDA_RWKV7g
+from .wkv7 import RUN_CUDA_RWKV7g, RUN_CUDA_RWKV7g_state
 
 
 def _stream(t):
@@ -1122,7 +1122,10 @@ def tmix_from_mixed(m, mixed, v_first, recompute_state=False):
             k2, v2, z, b, k2_b, v2_b = kva(k, v, v_first, vl, al, m.k_k, m.k_a, m.a0, m.v0, True)
         if not GRAD_ALIAS:
             k2_b, v2_b = k2, v2
-    y = RUN_CUDA_RWKV7g(r, w, k2, v2, z, b, recompute_state=recompute_state)
+    if getattr(m, "time_state", None) is not None:      # state tuning: the recurrence starts from the layer's learnable state
+        y, _ = RUN_CUDA_RWKV7g_state(r, w, k2, v2, z, b, m.wkv_initial_state(), recompute_state=recompute_state)
+    else:
+        y = RUN_CUDA_RWKV7g(r, w, k2, v2, z, b, recompute_state=recompute_state)
     y = post(y, r, k2_b, v2_b, g, m.ln_x.weight, m.ln_x.bias, m.r_k, m.ln_x.eps)
     return linear(m.output, y), v_first
 

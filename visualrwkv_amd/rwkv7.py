@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 from torch.nn import functional as F
 
-from .wkv7 import CHUNK_LEN, RUN_CUDA_RWKV7g
+from .wkv7 import CHUNK_LEN, RUN_CUDA_RWKV7g, RUN_CUDA_RWKV7g_state
 
 STOP_TOKEN_INDEX = 261        # src/dataset.py:20  ("\n\n"), used to left-pad to a multiple of CHUNK_LEN
 IGNORE_INDEX = -100           # src/dataset.py:17
@@ -99,9 +99,20 @@ class RWKV_Tmix_x070(nn.Module):
             self.key.weight.data.uniform_(-0.05 / (C ** 0.5), 0.05 / (C ** 0.5))
             self.value.weight.data.uniform_(-0.5 / (C ** 0.5), 0.5 / (C ** 0.5))
             self.output.weight.data.zero_()
+            if getattr(args, "state_tune", 0):
+                # state tuning (not in the reference): a learnable initial WKV state per head, [value row][key column] like every state of
+                # this package.  An ordinary parameter of the model's dtype; the op receives it in fp32 (wkv_initial_state)
+                self.time_state = nn.Parameter(torch.zeros(H, N, N))
+
+    def wkv_initial_state(self):
+        """The learnable initial WKV state (H,64,64) in the dtype the op takes (fp32; fp64 for an fp64 model), or None without state tuning."""
+        ts = getattr(self, "time_state", None)
+        if ts is None:
+            return None
+        return ts if ts.dtype == torch.float64 else ts.float()
 
     def forward(self, x, v_first, state=None):
-        """`state` (an RWKV7State, inference only) carries the previous token and the WKV state across calls."""
+        """`state` (an RWKV7State; inference: no gradient flows through it) carries the previous token and the WKV state across calls."""
         B, T, C = x.size()
         H = self.n_head
         if getattr(self.args, "fused", False) and x.is_cuda:
@@ -137,7 +148,9 @@ class RWKV_Tmix_x070(nn.Module):
         kk = F.normalize(kk.view(B, T, H, -1), dim=-1, p=2.0).view(B, T, C)
         k = k * (1 + (a - 1) * self.k_a)
 
-        if state is None:
+        if state is None and getattr(self, "time_state", None) is not None:
+            x, _ = RUN_CUDA_RWKV7g_state(r, w, k, v, -kk, kk * a, self.wkv_initial_state())
+        elif state is None:
             x = RUN_CUDA_RWKV7g(r, w, k, v, -kk, kk * a)
         else:
             x = state.wkv(self.layer_id, r, w, k, v, -kk, kk * a)
@@ -235,15 +248,21 @@ class RWKV7State:
     channel-mix shifts (the reference's ZeroPad2d shift sees zeros before the first token) and the WKV state
     S (B,H,64,64) fp32.  Whole 16-token chunks go through the chunked MFMA forward kernel continuing from S (cut into
     sequence-parallel segments when the heads alone cannot fill the chip); the ragged tail and single tokens are one
-    `wkv7_step` launch each."""
+    `wkv7_step` launch each.  With `blocks` (the model's Blocks) a layer that owns a tuned initial state (`time_state`, args.state_tune)
+    starts from it, broadcast over the batch, instead of from zeros."""
 
-    def __init__(self, args, batch, device, dtype=torch.bfloat16):
+    def __init__(self, args, batch, device, dtype=torch.bfloat16, blocks=None):
         L, C = args.n_layer, args.n_embd
         self.att_x = [torch.zeros(batch, C, device=device, dtype=dtype) for _ in range(L)]
         self.ffn_x = [torch.zeros(batch, C, device=device, dtype=dtype) for _ in range(L)]
         self.S = [torch.zeros(batch, args.dim_att // 64, 64, 64, device=device, dtype=torch.float32) for _ in range(L)]
         self.fresh = [True] * L
         self.n_tokens = 0
+        for i, blk in enumerate(blocks if blocks is not None else ()):
+            ts = getattr(blk.att, "time_state", None)
+            if ts is not None:
+                self.S[i].copy_(ts.detach().to(device=device, dtype=torch.float32).unsqueeze(0).expand_as(self.S[i]))
+                self.fresh[i] = False                   # the first chunks continue from S like every later one
 
     def wkv(self, layer, r, w, k, v, z, b):
         from . import wkv7
@@ -329,7 +348,7 @@ class RWKV(nn.Module):
         added: logits equal those `forward` gives for the same absolute positions of the concatenated sequence.
         Returns (logits (B,T,V) or (B,V) with last_only, state)."""
         if state is None:
-            state = RWKV7State(self.args, x.size(0), x.device, x.dtype)
+            state = RWKV7State(self.args, x.size(0), x.device, x.dtype, blocks=self.blocks)
         v_first = torch.empty_like(x)
         use_decode = False
         if getattr(self.args, "fused", False) and x.shape[1] == 1:

@@ -72,11 +72,22 @@ class VisualRWKV(nn.Module):
     def freeze_proj(self):
         self.proj.requires_grad_(False)
 
+    def freeze_for_state_tuning(self):
+        """State tuning (args.state_tune; not in the reference): every weight frozen, only the learnable initial WKV states
+        (`time_state` of every RWKV_Tmix_x070) train."""
+        states = [n for n, _ in self.named_parameters() if n.endswith(".time_state")]
+        if not states:
+            raise ValueError("freeze_for_state_tuning: the model has no time_state parameters (build it with args.state_tune = 1)")
+        for n, p in self.named_parameters():
+            p.requires_grad_(n.endswith(".time_state"))
+
     def optimizer_groups(self):
         """Parameter groups of configure_optimizers (src/model.py:390-410): tensors that are at least 2-D
-        after squeeze() get weight decay, everything else none."""
-        no_wd = [p for p in self.parameters() if p.requires_grad and len(p.squeeze().shape) < 2]
-        wd = [p for p in self.parameters() if p.requires_grad and len(p.squeeze().shape) >= 2]
+        after squeeze() get weight decay, everything else none.  The learnable initial states (`time_state`, args.state_tune) are a
+        starting point of the recurrence, not a weight: no decay."""
+        named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+        no_wd = [p for n, p in named if len(p.squeeze().shape) < 2 or n.endswith(".time_state")]
+        wd = [p for n, p in named if len(p.squeeze().shape) >= 2 and not n.endswith(".time_state")]
         groups = []
         if no_wd:
             groups.append({"params": no_wd, "weight_decay": 0.0})

@@ -267,6 +267,140 @@ def RUN_CUDA_RWKV7g(q, w, k, v, a, b, recompute_state=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Training with a carried state (state tuning, training across a cut in the sequence).  Not in the reference, whose
+# WindBackstepping has no state argument; the math is the recurrence of RWKV-v7_simple.py with an initial state.
+# ---------------------------------------------------------------------------------------------------------------
+def _native(t):
+    """Whether a call on `t` runs the library kernels (device tensors) or this module's PyTorch recurrence (CPU tensors)."""
+    return t.is_cuda
+
+
+def _wkv7_state_torch(w, q, k, v, z, a, state0):
+    """The recurrence in plain PyTorch, differentiable: fp64 for fp64 inputs, else fp32.  Returns (y, state_T) in that dtype."""
+    dt = torch.float64 if w.dtype == torch.float64 else torch.float32
+    w, q, k, v, z, a = [x.to(dt) for x in (w, q, k, v, z, a)]
+    state = state0.to(dt)
+    decay = torch.exp(-torch.exp(w))
+    ys = []
+    for t in range(w.shape[1]):
+        sa = state @ z[:, t].unsqueeze(-1)                                   # (B,H,N,1)
+        state = state * decay[:, t, :, None, :] + sa @ a[:, t].unsqueeze(-2) + v[:, t].unsqueeze(-1) * k[:, t].unsqueeze(-2)
+        ys.append((state @ q[:, t].unsqueeze(-1)).squeeze(-1))
+    return torch.stack(ys, dim=1), state
+
+
+def wkv7_backward_state(w, q, k, v, z, a, dy, s, sa, state0=None, ds_final=None, want_ds0=True):
+    """vrwkv_wkv7_backward_state_bf16: the training backward from a forward that started at `state0` (None = zeros) with dL/d(state_T) =
+    `ds_final` (None = zeros).  Returns (dw, dq, dk, dv, dz, da, ds0 or None); states are (B,H,64,64) fp32, [value row][key column]."""
+    B, T, H = _dims(w)
+    for n, t in zip(("w", "q", "k", "v", "z", "a", "dy"), (w, q, k, v, z, a, dy)):
+        _check_act(n, t, B, T, H)
+    _check_state(s, sa, B, T, H, w.device)
+    for n, t in (("state0", state0), ("ds_final", ds_final)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, H, HEAD_SIZE, HEAD_SIZE)
+                              or t.device != w.device):
+            raise ValueError(f"wkv7: {n} must be a contiguous fp32 ({B},{H},{HEAD_SIZE},{HEAD_SIZE}) tensor on {w.device}")
+    grads = [torch.empty_like(w) for _ in range(6)]
+    ds0 = torch.empty(B, H, HEAD_SIZE, HEAD_SIZE, dtype=torch.float32, device=w.device) if want_ds0 else None
+    lib = hip_lib.load()
+    ptr = lambda t: t.data_ptr() if t is not None else 0
+    with torch.cuda.device(w.device):
+        stream = torch.cuda.current_stream(w.device).cuda_stream
+        rc = _timed("bwd_state", B * T * H * HEAD_SIZE, w.device, lambda: lib.vrwkv_wkv7_backward_state_bf16(
+            B, T, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(), a.data_ptr(), dy.data_ptr(),
+            s.data_ptr(), sa.data_ptr(), ptr(state0), ptr(ds_final), ptr(ds0), *[g.data_ptr() for g in grads], stream))
+    hip_lib.check(rc, "vrwkv_wkv7_backward_state_bf16")
+    return (*grads, ds0)
+
+
+class WindBacksteppingState(torch.autograd.Function):
+    """WindBackstepping with a carried state: (w, q, k, v, z, b, state0, recompute_state=False) -> (y, state_T).
+
+    state0 / state_T: (B,H,64,64) fp32 in [value row][key column] order; both take part in autograd (dL/d state_T comes in,
+    dL/d state0 goes out), which is what a learnable initial state and training across a cut in the sequence need.
+    Device tensors (bf16): vrwkv_wkv7_forward_state_bf16 with the training by-products, vrwkv_wkv7_backward_state_bf16.
+    recompute_state=True keeps neither `s` nor `sa` and regenerates them in the backward FROM state0 (fused.blocks_forward's
+    memory mode 2).  The sequence-parallel training path (TPARALLEL_BWD) is not used here: the sequential kernels run whatever
+    the number of heads.
+    CPU tensors: a plain PyTorch recurrence (fp32 for bf16 / fp32 inputs, fp64 for fp64 ones) whose backward is torch autograd
+    through a recomputation -- slow, meant for tests and small models."""
+
+    @staticmethod
+    def forward(ctx, w, q, k, v, z, b, state0, recompute_state=False):
+        B, T, H, C = w.shape
+        assert T % CHUNK_LEN == 0
+        assert all(i.is_contiguous() for i in [w, q, k, v, z, b, state0])
+        assert tuple(state0.shape) == (B, H, C, C)
+        ctx.set_materialize_grads(False)
+        ctx.native = _native(w)
+        if not ctx.native:
+            with torch.no_grad():
+                y, fin = _wkv7_state_torch(w, q, k, v, z, b, state0)
+            ctx.save_for_backward(w, q, k, v, z, b, state0)
+            return y.to(v.dtype), fin.to(state0.dtype)
+        assert all(i.dtype == torch.bfloat16 for i in [w, q, k, v, z, b]) and state0.dtype == torch.float32
+        if not any(ctx.needs_input_grad[:7]):            # nobody will ask for a gradient: no by-products
+            ctx.recompute = False
+            return wkv7_forward_state(w, q, k, v, z, b, state0, want_state=True)
+        ctx.recompute = bool(recompute_state)
+        if ctx.recompute:
+            y, fin = wkv7_forward_state(w, q, k, v, z, b, state0, want_state=True)
+            ctx.save_for_backward(w, q, k, v, z, b, state0)
+            return y, fin
+        s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
+        sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+        y, fin = wkv7_forward_state(w, q, k, v, z, b, state0, want_state=True, s_ckpt=s, sa=sa)
+        ctx.save_for_backward(w, q, k, v, z, b, state0, s, sa)
+        return y, fin
+
+    @staticmethod
+    def backward(ctx, dy, dfin):
+        want_ds0 = ctx.needs_input_grad[6]
+        if not ctx.native:
+            w, q, k, v, z, b, state0 = ctx.saved_tensors
+            with torch.enable_grad():
+                leaves = [x.detach().requires_grad_(True) for x in (w, q, k, v, z, b, state0)]
+                y, fin = _wkv7_state_torch(*leaves)
+                loss = 0
+                if dy is not None:
+                    loss = loss + (y * dy.to(y.dtype)).sum()
+                if dfin is not None:
+                    loss = loss + (fin * dfin.to(fin.dtype)).sum()
+                g = torch.autograd.grad(loss, leaves, allow_unused=True)
+            g = [torch.zeros_like(l) if x is None else x for x, l in zip(g, leaves)]
+            return (*g[:6], g[6] if want_ds0 else None, None)
+        if ctx.recompute:
+            w, q, k, v, z, b, state0 = ctx.saved_tensors
+            B, T, H, C = w.shape
+            s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
+            sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+            wkv7_forward_state(w, q, k, v, z, b, state0, want_state=False, s_ckpt=s, sa=sa)
+        else:
+            w, q, k, v, z, b, state0, s, sa = ctx.saved_tensors
+        if dy is None:
+            dy = torch.zeros_like(v)
+        assert dy.dtype == w.dtype
+        dy = dy.contiguous()
+        if dfin is not None:
+            dfin = dfin.float().contiguous()
+        *grads, ds0 = wkv7_backward_state(w, q, k, v, z, b, dy, s, sa, state0, dfin, want_ds0)
+        return (*grads, ds0, None)
+
+
+def RUN_CUDA_RWKV7g_state(q, w, k, v, a, b, state0, recompute_state=False):
+    """RUN_CUDA_RWKV7g from a state: (B,T,HC) views -> (B,T,H,64), the same (w,q,...) re-order; returns (y (B,T,HC), state_T (B,H,64,64)).
+    state0: (B,H,64,64), or (H,64,64) = one state for every sample -- it is broadcast over the batch and its gradient is the sum over the
+    batch, accumulated in fp32 (autograd's reduction of the expanded view)."""
+    B, T, HC = q.shape
+    H = HC // 64
+    q, w, k, v, a, b = [i.view(B, T, H, 64) for i in [q, w, k, v, a, b]]
+    if state0.dim() == 3:
+        state0 = state0.unsqueeze(0).expand(B, H, 64, 64)
+    y, fin = WindBacksteppingState.apply(w, q, k, v, a, b, state0.contiguous(), recompute_state)
+    return y.view(B, T, HC), fin
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Stateful generation (SURVEY.md 8f rank 1).  Not in the reference, whose generate() re-runs the full forward for
 # every new token (src/model.py:513-529); same recurrence, state carried between calls.
 # ---------------------------------------------------------------------------------------------------------------
