@@ -87,6 +87,30 @@ int vrwkv_wkv7_backward_state_bf16(int B, int T, int H, const void* w, const voi
                                    const float* s0, const float* ds_final, float* ds0,
                                    void* dw, void* dq, void* dk, void* dv, void* dz, void* da, void* stream);
 
+/* Packed rows (sample packing; no counterpart in the reference, which pads every sample to ctx_len): a row of T tokens holds several samples
+ * end to end, each a whole number of 16-token chunks.  chunk_reset: device, (B, T/16) bytes; a non-zero chunk_reset[b][c] means chunk c of
+ * row b starts from S = 0 (chunk 0 always does), and in the backward no dL/dS flows from chunk c into chunk c-1.  Every sample gets what a
+ * launch on its rows alone gives, bit for bit: y, sa, the six gradients, and s_ckpt[b][h][c] = the state at the end of chunk c of the walk
+ * WITH the resets, which is what the backward expects in `s`.  One exception, on purpose: dw of the first token of a flagged chunk is written
+ * as 0, its exact value (w of that token multiplies the zero state before it), where a plain launch leaves a cancellation residue.  This
+ * follows the FLAG: chunk 0 starts from S = 0 with or without its flag, but only a set chunk_reset[b][0] zeroes dw of token 0 (all-zero flags
+ * must reproduce the plain entry).  visualrwkv_amd/wkv7.py::PackedLayout sets it, and the per-segment paths of that module write the same zeros.
+ * The kernels read the flags in aligned 4-byte granules: up to 3 bytes before / after the (B, T/16) array are loaded and ignored, so the
+ * array must lie in a device allocation that contains them (any allocator's granule does; mind this when passing a sub-array).  chunk_reset == NULL or all zeros: the results of vrwkv_wkv7_forward_bf16 (where
+ * that runs csrc/wkv7_fwd_v4.h) / vrwkv_wkv7_backward_bf16, bit for bit.
+ *   forward:  always csrc/wkv7_fwd_v4.h (variant 7: it runs at any number of heads), whatever vrwkv_wkv7_set_forward_variant says;
+ *             s_ckpt / sa may be NULL together (no by-products).
+ *   backward: csrc/wkv7_bwd_v8.h, schedules 8 / 9 by the rule and the override of vrwkv_wkv7_backward_bf16, the same batch slices (chunk_reset
+ *             is sliced by row).  The sequence-parallel kernel has no resets: with the override at 5, or for a single sample of 4 GiB and
+ *             more, VRWKV_ESHAPE (run the samples one by one then: visualrwkv_amd/wkv7.py::WindBacksteppingPacked does). */
+int vrwkv_wkv7_forward_packed_bf16(int B, int T, int H, const void* w, const void* q, const void* k, const void* v,
+                                   const void* z, const void* a, void* y, const unsigned char* chunk_reset,
+                                   float* s_ckpt, float* sa, void* stream);
+int vrwkv_wkv7_backward_packed_bf16(int B, int T, int H, const void* w, const void* q, const void* k, const void* v,
+                                    const void* z, const void* a, const void* dy, const float* s, const float* sa,
+                                    const unsigned char* chunk_reset,
+                                    void* dw, void* dq, void* dk, void* dv, void* dz, void* da, void* stream);
+
 /* WKV6 (BASELINE config 4): replaces cuda_forward / cuda_backward of VisualRWKV-v6/v6.0/cuda/wkv6_cuda.cu:229-242 as bound
  * by cuda/wkv6_op.cpp:8-13 (forward(B,T,C,H,r,k,v,w,u,y), backward(B,T,C,H,r,k,v,w,u,gy,gr,gk,gv,gw,gu)).
  * r,k,v,y,gy,gr,gk,gv,gw: (B,T,C) bf16; ew: (B,T,C) f32 = -exp(w_raw) as WKV_6.forward computes it (src/model.py:62);
@@ -135,6 +159,18 @@ int vrwkv_ln_mix_bwd_bf16(long ntok, int T, int C, int M, const void* xn, const 
 int vrwkv_mix_bwd_ln_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
                           const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second, void* dx,
                           float* dmu, float* ws, void* stream);
+/* The three entries above for packed rows (several samples end to end in a row of T tokens; visualrwkv_amd/wkv7.py::PackedLayout): one more
+ * argument, `first` (ntok bytes on the device).  The shifted value is zero where first[n] != 0 OR n % T == 0, and in the backward no gradient
+ * goes from such a row n to row n-1.  first == NULL: the entry above, bit for bit (the same kernel templates with the pointer switched off). */
+int vrwkv_ln_mix_fwd_packed_bf16(long ntok, int T, int C, float eps, int M, const void* x, const void* delta, const void* w, const void* b,
+                                 const void* const* mu, void* xn, void* const* out, float* mean, float* rstd, const unsigned char* first,
+                                 void* stream);
+int vrwkv_ln_mix_bwd_packed_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* w,
+                                 const void* b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* dres,
+                                 const unsigned char* first, void* dx, float* dwb, float* dmu, float* ws, void* stream);
+int vrwkv_mix_bwd_ln_packed_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
+                                 const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second,
+                                 const unsigned char* first, void* dx, float* dmu, float* ws, void* stream);
 /* Inference form for the frozen ViT towers: xn = x + delta * dscale (dscale = LayerScale gamma (C) bf16 or NULL; delta NULL: no
  * add, xn not written), y = LayerNorm(xn); no statistics kept (timm blocks via src/vision.py:123-134, src/sam.py:231-247). */
 int vrwkv_add_ln_scaled_fwd_bf16(long ntok, int C, float eps, const void* x, const void* delta, const void* dscale, const void* w,
@@ -234,11 +270,13 @@ int vrwkv_wkv7_set_backward_variant(int variant);
 int vrwkv_wkv7_set_backward_slice_limit(unsigned long long bytes);
 /* The kernel generation the LAST vrwkv_wkv7_forward_bf16 (backward == 0) / vrwkv_wkv7_backward_bf16 or vrwkv_wkv7_backward_state_bf16 (backward != 0) launch of this
  * process resolved to, in the numbering above (forward: 7 = wkv7_fwd_v4.h, 6 = two workgroups per head, 4 = wkv7_fwd_v3.h; 0 = none yet);
- * vrwkv_wkv7_forward_state_bf16 records into the forward slot as well.  Lets a single-threaded parity test assert WHICH kernel the default
+ * vrwkv_wkv7_forward_state_bf16 and vrwkv_wkv7_forward_packed_bf16 record into the forward slot as well, vrwkv_wkv7_backward_packed_bf16 into the
+ * backward slot.  Lets a single-threaded parity test assert WHICH kernel the default
  * dispatch chose for its shape. */
 int vrwkv_wkv7_last_variant(int backward);
 /* Which kernel generation a launch of shape (B,T,H) resolves to under the current override, WITHOUT launching: kind 0 = vrwkv_wkv7_forward_bf16,
- * 1 = vrwkv_wkv7_backward_bf16, 2 = vrwkv_wkv7_forward_state_bf16 (same rule as kind 0; its A/B overrides 1..5 all mean 4), 3 = vrwkv_wkv7_backward_state_bf16 (same rule as kind 1).  A pure function of
+ * 1 = vrwkv_wkv7_backward_bf16, 2 = vrwkv_wkv7_forward_state_bf16 (same rule as kind 0; its A/B overrides 1..5 all mean 4), 3 = vrwkv_wkv7_backward_state_bf16 (same rule as kind 1),
+ * 4 = vrwkv_wkv7_forward_packed_bf16 (always 7), 5 = vrwkv_wkv7_backward_packed_bf16 (same rule as kind 1; an answer of 5 means that entry returns VRWKV_ESHAPE).  A pure function of
  * its arguments and the override: unlike vrwkv_wkv7_last_variant it does not depend on which thread launched last (the reference calls the op
  * from the Python thread and from autograd's backward thread).  A bad shape or kind gives VRWKV_EINVAL (< 0). */
 int vrwkv_wkv7_resolve_variant(int kind, int B, int T, int H);

@@ -123,6 +123,13 @@ long vrwkv_ln_mix_ws_floats(long ntok, int C, int M) { return (long)ln_mix_bwd_g
 
 int vrwkv_ln_mix_fwd_bf16(long ntok, int T, int C, float eps, int M, const void* x, const void* delta, const void* w, const void* b,
                           const void* const* mu, void* xn, void* const* out, float* mean, float* rstd, void* stream) {
+    return vrwkv_ln_mix_fwd_packed_bf16(ntok, T, C, eps, M, x, delta, w, b, mu, xn, out, mean, rstd, nullptr, stream);
+}
+
+// the same with sample boundaries inside the rows: first[n] != 0 (ntok bytes) = row n reads zeros for its shifted value; NULL = the entry above
+int vrwkv_ln_mix_fwd_packed_bf16(long ntok, int T, int C, float eps, int M, const void* x, const void* delta, const void* w, const void* b,
+                                 const void* const* mu, void* xn, void* const* out, float* mean, float* rstd, const unsigned char* first,
+                                 void* stream) {
     if (ntok <= 0 || T <= 0 || ntok % T != 0 || !x || !w || !b || !mu || !out || !mean || !rstd || (delta && !xn)) return VRWKV_EINVAL;
     if (!ln_ok(C) || (M != 1 && M != 6)) return VRWKV_ESHAPE;
     LmPtrs pm{}; LmOuts po{};
@@ -132,7 +139,11 @@ int vrwkv_ln_mix_fwd_bf16(long ntok, int T, int C, float eps, int M, const void*
     }
     const dim3 grid(ln_grid(ntok, LN_MIX_ROWS_PER_WG)), block(ln_threads(C));
     hipStream_t st = (hipStream_t)stream;
-    if (M == 1) hipLaunchKernelGGL(ln_mix_fwd_kernel<1>, grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
+    if (first && M == 1) hipLaunchKernelGGL((ln_mix_fwd_kernel<1, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
+                                            (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po, first);
+    else if (first) hipLaunchKernelGGL((ln_mix_fwd_kernel<6, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
+                                       (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po, first);
+    else if (M == 1) hipLaunchKernelGGL(ln_mix_fwd_kernel<1>, grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
                                    (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po);
     else hipLaunchKernelGGL(ln_mix_fwd_kernel<6>, grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
                             (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po);
@@ -147,6 +158,13 @@ int vrwkv_ln_mix_fwd_bf16(long ntok, int T, int C, float eps, int M, const void*
 int vrwkv_ln_mix_bwd_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* w,
                           const void* b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* dres,
                           void* dx, float* dwb, float* dmu, float* ws, void* stream) {
+    return vrwkv_ln_mix_bwd_packed_bf16(ntok, T, C, M, xn, mean, rstd, w, b, mu, dout, dout3_second, dres, nullptr, dx, dwb, dmu, ws, stream);
+}
+
+// the same with sample boundaries inside the rows: first[n] != 0 (ntok bytes) = no gradient from row n to row n-1; NULL = the entry above
+int vrwkv_ln_mix_bwd_packed_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* w,
+                                 const void* b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* dres,
+                                 const unsigned char* first, void* dx, float* dwb, float* dmu, float* ws, void* stream) {
     if (ntok <= 0 || T <= 0 || ntok % T != 0 || !xn || !mean || !rstd || !w || !b || !mu || !dout || !dx || !dwb || !dmu || !ws) return VRWKV_EINVAL;
     if (!ln_ok(C) || M != 1 || dout3_second) return VRWKV_ESHAPE;        // M = 6: vrwkv_mix_bwd_ln_bf16 + vrwkv_add_ln_bwd_bf16 (below)
     LmPtrs pm{}, pd{};
@@ -158,11 +176,11 @@ int vrwkv_ln_mix_bwd_bf16(long ntok, int T, int C, int M, const void* xn, const 
     const dim3 grid(G), block(ln_threads(C));
     hipStream_t st = (hipStream_t)stream;
     float* part_ln = ws; float* part_mu = ws + (size_t)G * 2 * C;
-#define LN_MIX_BWD_LB(MM, DUP, LB) hipLaunchKernelGGL((ln_mix_bwd_kernel<MM, DUP, LB>), grid, block, 0, st, ntok, T, C, (const uint16_t*)xn, mean, rstd, \
-        (const uint16_t*)w, (const uint16_t*)b, pm, pd, (const uint16_t*)dout3_second, (const uint16_t*)dres, (uint16_t*)dx, part_ln, part_mu)
-#define LN_MIX_BWD(MM, DUP) do { if (block.x <= 256) LN_MIX_BWD_LB(MM, DUP, 256); else if (block.x <= 512) LN_MIX_BWD_LB(MM, DUP, 512); \
-                                 else LN_MIX_BWD_LB(MM, DUP, 1024); } while (0)
-    LN_MIX_BWD(1, false);
+#define LN_MIX_BWD_LB(MM, DUP, LB, PK) hipLaunchKernelGGL((ln_mix_bwd_kernel<MM, DUP, LB, PK>), grid, block, 0, st, ntok, T, C, (const uint16_t*)xn, mean, rstd, \
+        (const uint16_t*)w, (const uint16_t*)b, pm, pd, (const uint16_t*)dout3_second, (const uint16_t*)dres, (uint16_t*)dx, part_ln, part_mu, first)
+#define LN_MIX_BWD(MM, DUP, PK) do { if (block.x <= 256) LN_MIX_BWD_LB(MM, DUP, 256, PK); else if (block.x <= 512) LN_MIX_BWD_LB(MM, DUP, 512, PK); \
+                                     else LN_MIX_BWD_LB(MM, DUP, 1024, PK); } while (0)
+    if (first) LN_MIX_BWD(1, false, true); else LN_MIX_BWD(1, false, false);
 #undef LN_MIX_BWD
 #undef LN_MIX_BWD_LB
     hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, st, G, 2L * C, part_ln, dwb);

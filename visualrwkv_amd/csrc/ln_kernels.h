@@ -220,11 +220,14 @@ __global__ __launch_bounds__(256) void ln_colsum_kernel(int G, long width, const
 struct LmPtrs { const uint16_t* p[6]; };
 struct LmOuts { uint16_t* p[6]; };
 
-template <int M>
+// PK (the _packed entries: rows that hold several samples end to end): first_tok[n] != 0 marks the first token of a sample next to n % T == 0;
+// one byte per 2 C-byte row, read once per row at a wave-uniform address.  With PK off the pointer is never read.
+template <int M, bool PK = false>
 __global__ __launch_bounds__(1024) void ln_mix_fwd_kernel(long ntok, int T, int C, float eps, const uint16_t* __restrict__ x,
                                                           const uint16_t* __restrict__ delta, const uint16_t* __restrict__ w,
                                                           const uint16_t* __restrict__ b, uint16_t* __restrict__ xn,
-                                                          float* __restrict__ mean, float* __restrict__ rstd, LmPtrs mu, LmOuts out) {
+                                                          float* __restrict__ mean, float* __restrict__ rstd, LmPtrs mu, LmOuts out,
+                                                          const unsigned char* __restrict__ first_tok = nullptr) {
     __shared__ float red[4][MAXW][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int c0 = threadIdx.x * 8;
@@ -275,7 +278,7 @@ __global__ __launch_bounds__(1024) void ln_mix_fwd_kernel(long ntok, int T, int 
         for (int e = 0; e < 8; ++e) o.f[e] = fmaf((v.f[e] - mu_) * rs, wv.f[e], bv.f[e]);
         const V8 cur = unpack8(pack8(o));                        // the bf16 value the two-kernel path stores and re-reads
         if (own) {
-            const bool first = tpos == 0;
+            const bool first = tpos == 0 || (PK && first_tok[n] != 0);
             V8 xx;
 #pragma unroll
             for (int e = 0; e < 8; ++e) xx.f[e] = (first ? 0.f : prev.f[e]) - cur.f[e];
@@ -321,13 +324,14 @@ DEVFN void ln_row_bwd(float (*red)[MAXW][2], int slot, int wave, int lane, int n
 // gradient accumulators per thread): rows travel packed (bf16) and are unpacked where used, the previous row is carried as packed
 // xn + its two statistics and its LayerNorm output is recomputed, and the next row's loads are issued after this row's values
 // have been consumed and before the reduction -- the kernel needs ~2 us of HBM time per row and CU, the arithmetic ~0.3.
-template <int M, bool DUP3, int LB>
+template <int M, bool DUP3, int LB, bool PK = false>
 __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long ntok, int T, int C, const uint16_t* __restrict__ xn,
                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
                                                         const uint16_t* __restrict__ w, const uint16_t* __restrict__ b, LmPtrs mu,
                                                         LmPtrs dout, const uint16_t* __restrict__ dout3b,
                                                         const uint16_t* __restrict__ dres, uint16_t* __restrict__ dx,
-                                                        float* __restrict__ part_ln, float* __restrict__ part_mu) {
+                                                        float* __restrict__ part_ln, float* __restrict__ part_mu,
+                                                        const unsigned char* __restrict__ first_tok = nullptr) {
     __shared__ float red[2][MAXW][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int c0 = threadIdx.x * 8;
@@ -375,7 +379,7 @@ __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long 
         int slot = 0;
         int tpos = (int)(lo % T);                                // position of row n inside its sample
         for (long n = lo; n <= last; ++n) {
-            const bool inside = n < hi, cont = tpos != 0;
+            const bool inside = n < hi, cont = tpos != 0 && !(PK && first_tok[n] != 0);      // PK: nothing goes from a sample's first row to the row before
             keep_packed(wp); keep_packed(bp);
 #pragma unroll
             for (int j = 0; j < M; ++j) keep_packed(mp[j]);

@@ -187,10 +187,12 @@ DEVFN void st4f(uint16_t* p, const V4& v) {
 // LNX: x is not stored -- it is the LayerNorm output of the fused add + LayerNorm + lerps forward (ln_fused.hip: ln_mix_fwd_kernel),
 // recomputed here from xn and the row statistics exactly as that kernel rounded it: bf16(fma((xn - mean) rstd, gamma, beta)).
 struct LnX { const float* mean; const float* rstd; const uint16_t* w; const uint16_t* b; };
-template <int M, bool DUP3, bool DD = false, bool LNX = false>
+// PK (vrwkv_mix_bwd_ln_packed_bf16: rows that hold several samples end to end): first_tok[n] != 0 marks a sample's first token next to n % T == 0.
+template <int M, bool DUP3, bool DD = false, bool LNX = false, bool PK = false>
 __global__ __launch_bounds__(512) void mix_bwd_kernel(long ntok, int T, int C, const uint16_t* __restrict__ x, Ptrs6 mu, Ptrs6 dout,
                                                       const uint16_t* __restrict__ dout3b, uint16_t* __restrict__ dx,
-                                                      float* __restrict__ dmu, Ptrs6 mm = Ptrs6{}, MPtrs6 dmm = MPtrs6{}, LnX ln = LnX{}) {
+                                                      float* __restrict__ dmu, Ptrs6 mm = Ptrs6{}, MPtrs6 dmm = MPtrs6{}, LnX ln = LnX{},
+                                                      const unsigned char* __restrict__ first_tok = nullptr) {
     const long lo = ntok * blockIdx.x / gridDim.x, hi = ntok * (blockIdx.x + 1) / gridDim.x;
     for (int c0 = threadIdx.x * 4; c0 < C; c0 += blockDim.x * 4) {
         uint2 lnw = make_uint2(0u, 0u), lnb = lnw;
@@ -227,7 +229,7 @@ __global__ __launch_bounds__(512) void mix_bwd_kernel(long ntok, int T, int C, c
 #pragma unroll 4
         for (long n = lo; n <= last; ++n) {
             const bool inside = n < hi;
-            const bool cont = n % T != 0;                   // row n-1 belongs to the same sequence
+            const bool cont = n % T != 0 && !(PK && first_tok[n] != 0);      // row n-1 belongs to the same sequence (and the same sample)
             V4 d[M];
 #pragma unroll
             for (int j = 0; j < M; ++j) d[j] = ld4f(dout.p[j] + n * C + c0);
@@ -740,6 +742,13 @@ int vrwkv_mix_bwd2_bf16(long ntok, int T, int C, int M, const void* x, const voi
 int vrwkv_mix_bwd_ln_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
                           const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second, void* dx,
                           float* dmu, float* ws, void* stream) {
+    return vrwkv_mix_bwd_ln_packed_bf16(ntok, T, C, M, xn, mean, rstd, ln_w, ln_b, mu, dout, dout3_second, nullptr, dx, dmu, ws, stream);
+}
+
+// the same with sample boundaries inside the rows: first[n] != 0 (ntok bytes) = no gradient from row n to row n-1; NULL = the entry above
+int vrwkv_mix_bwd_ln_packed_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
+                                 const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second,
+                                 const unsigned char* first, void* dx, float* dmu, float* ws, void* stream) {
     if (ntok <= 0 || T <= 0 || !xn || !mean || !rstd || !ln_w || !ln_b || !mu || !dout || !dx || !dmu || !ws || M != 6) return VRWKV_EINVAL;
     if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
     Ptrs6 m{}, d{};
@@ -749,7 +758,9 @@ int vrwkv_mix_bwd_ln_bf16(long ntok, int T, int C, int M, const void* xn, const 
     const int threads = C / 4 < 512 ? C / 4 : 512;
     const uint16_t* d2 = (const uint16_t*)dout3_second;
     const LnX ln{mean, rstd, (const uint16_t*)ln_w, (const uint16_t*)ln_b};
-    if (d2) hipLaunchKernelGGL((mix_bwd_kernel<6, true, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln);
+    if (first && d2) hipLaunchKernelGGL((mix_bwd_kernel<6, true, false, true, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln, first);
+    else if (first) hipLaunchKernelGGL((mix_bwd_kernel<6, false, false, true, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln, first);
+    else if (d2) hipLaunchKernelGGL((mix_bwd_kernel<6, true, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln);
     else hipLaunchKernelGGL((mix_bwd_kernel<6, false, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln);
     colsum(G, (long)M * C, ws, dmu, st);
     return done();

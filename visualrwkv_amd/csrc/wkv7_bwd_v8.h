@@ -32,6 +32,7 @@
 namespace wkv7v8 {
 
 using wkv7::BwdArgs;
+using wkv7::uniform_flag_u8;
 using namespace wkv7c;
 using namespace wkv7v5;      // IMG, HLI, img_off, f32_off, LaneAddr, lane_addr, ld16, st16, mfma32, dot64, mask_split, tiles_op, dma_state
 using wkv7v6::Decay;
@@ -148,7 +149,10 @@ DEVFN Prep8 prep8(ChunkImg7& B, const RawP& raw, int c16, int j0, const LaneAddr
     if (c16 == 15) *reinterpret_cast<float4*>(&B.cl[j0]) = make_float4(o.cc[0], o.cc[1], o.cc[2], o.cc[3]);
     return o;
 }
-DEVFN void tail8(LdsV8& lds, int par, const TailQ& tr, const BwdArgs& p, size_t u, unsigned lane_boff, int c16, int pw, int g, const LaneAddr& la) {
+// zero_first (PACKED, wave-uniform): the chunk starts a sample from S = 0, so dL/dw of its first token is exactly 0 (w_0 multiplies the state
+// before it); the sum below leaves a cancellation residue there (~1e-4 of a typical |dw|), which is replaced by the exact value.
+DEVFN void tail8(LdsV8& lds, int par, const TailQ& tr, const BwdArgs& p, size_t u, unsigned lane_boff, int c16, int pw, int g, const LaneAddr& la,
+                 bool zero_first = false) {
     const float4 zt4 = *reinterpret_cast<const float4*>(&lds.res[0][la.f32]);
     const float4 qt4 = *reinterpret_cast<const float4*>(&lds.res[1][la.f32]);
     const float4 ah4 = *reinterpret_cast<const float4*>(&lds.res[2][la.f32]);
@@ -171,6 +175,7 @@ DEVFN void tail8(LdsV8& lds, int par, const TailQ& tr, const BwdArgs& p, size_t 
         if (c16 == 15) gt += glv[e];
         gt += dpp_shl<1>(gt); gt += dpp_shl<2>(gt); gt += dpp_shl<4>(gt); gt += dpp_shl<8>(gt);   // suffix sum over t
         dw[e] = gt * (l2 * LN2);
+        if (zero_first && c16 == 0) dw[e] = 0.f;
     }
     auto out = [&](uint16_t* base) { return reinterpret_cast<uint2*>(reinterpret_cast<char*>(base + u) + lane_boff); };   // uniform base + lane offset
     *out(p.dw) = make_uint2(cvt_pk_bf16(dw[0], dw[1]), cvt_pk_bf16(dw[2], dw[3]));
@@ -196,7 +201,25 @@ DEVFN void tail8(LdsV8& lds, int par, const TailQ& tr, const BwdArgs& p, size_t 
 //   * S0 of chunk 0 is s0[b,h] (the state the forward started from; null = 0) instead of zeros: the P waves fill the image through registers
 //     (the checkpoints hold S^T, states are [i][j]: LDS-DMA cannot transpose) in the ragged step that zero-fills it otherwise.
 // No new role, no new LDS image, no change to a steady-state (FULL) step.  With STATE off every `if (STATE ...)` folds away.
-template <bool PROF, bool AHEAD = false, bool STATE = false>
+// PACKED (vrwkv_wkv7_backward_packed_bf16): a row holds several samples end to end, each a whole number of chunks; BwdArgs::chunk_reset[b][c] != 0
+// says chunk c starts a sample (read as a scalar where it is used: uniform_flag_u8).  A chunk step is a function of the chunk's rows, its S0
+// and the incoming dL/dS, and those two are the only things that cross a boundary, each with one home:
+//   * S0 of a flagged chunk is zeros, not s[c-1].  The ragged steps pass nullptr to dma_state, the path chunk 0 takes anyway; the steady-state
+//     step stays free of conditions by selecting the SOURCE of its requests: 16 KB of zeros in device memory (zero_state) instead of s[cd-1];
+//   * the I waves zero dS1 -- the only copy of dL/dS -- after the step of a flagged chunk, before the hand-over image of the next step is
+//     formed from it, so the chunk below (the last chunk of the sample before) sees dL/dS = 0 like the last chunk of a launch.
+//   The J waves need nothing: they re-use the S0 operands of chunk c+1 as S_L of chunk c, and across a boundary S0(c+1) = 0 while S_L(c) = s[c].
+//   But S_L enters only the decay-gradient diagonal (dU)^T S_L, and there dU, formed from the zeroed dS1, is zero: the product is 0 whatever
+//   S_L is, and the zero operands are exactly what the last chunk of a plain launch multiplies by (s0h_p / s0l_p start as zeros).  So every
+//   chunk of a packed row goes through the arithmetic of the same chunk in a launch of its sample alone: the results are bit-identical
+//   (tests/test_emulated_wkv7_packed.py), with ONE exception made on purpose:
+//   * the tail writes dw = 0 at the first token of a flagged chunk (chunk 0 included when its flag is set).  That is the exact value -- w of
+//     that token multiplies the zero state before it -- where the plain kernel, which does not know that a launch starts from zero, leaves
+//     the cancellation residue of its sum (~5e-5 against |dw| ~ 0.3).  In a packed row 1 / (tokens of a sample) of dw are such elements.
+//   PACKED is not combined with STATE.  With PACKED off every `if (PACKED ...)` folds away.
+static __device__ float zero_state[N * N];               // never written
+
+template <bool PROF, bool AHEAD = false, bool STATE = false, bool PACKED = false>
 __global__ __launch_bounds__(768) void bwd_kernel_v8(BwdArgs p) {
     LdsV8& lds = *reinterpret_cast<LdsV8*>(dyn_lds());
     const int T = p.T, H = p.H;
@@ -209,6 +232,7 @@ __global__ __launch_bounds__(768) void bwd_kernel_v8(BwdArgs p) {
     const unsigned bh = blockIdx.x;
     const size_t head_base = ((size_t)(bh / H) * T * H + (bh % H)) * N;
     const float* sbase = p.s + (size_t)bh * nchunk * N * N;
+    const unsigned char* rs = PACKED ? p.chunk_reset + (size_t)(bh / H) * nchunk : nullptr;      // this row's flags
     const int nsteps = nchunk + 3;                      // the last step holds only the tail of chunk 0
     const LaneAddr la = lane_addr(c16, g, w);
     const unsigned out_off = (unsigned)c16 * ts + 16u * w + 4u * g;        // token c16, channels 16w+4g..+3
@@ -273,11 +297,19 @@ __global__ __launch_bounds__(768) void bwd_kernel_v8(BwdArgs p) {
                 const int k0 = w == 1 ? 0 : w == 2 ? 5 : 10, k1 = w == 0 ? 0 : w == 1 ? 5 : w == 2 ? 10 : 16;      // waves 1-3: 5 5 6 KB
                 if (FULL) {
                     const float* sc = sbase + (size_t)(cd - 1) * N * N;
+                    // (`if constexpr`: a discarded statement captures nothing, so the closure -- and with it the code of the other instantiations -- is unchanged)
+                    if constexpr (PACKED) sc = uniform_flag_u8(rs, cd) ? zero_state : sc;
                     if (w == 1) s0_lean<0>(lds, sc, ll); else if (w == 2) s0_lean<1>(lds, sc, ll); else if (w == 3) s0_lean<2>(lds, sc, ll);
                 } else if (STATE && cd == 0 && p.s0) fill_state_T(lds.s0, p.s0 + (size_t)bh * N * N, k0, k1, lane);
-                else if (cd >= 0 && cd <= nchunk - 1) dma_state(lds.s0, cd > 0 ? sbase + (size_t)(cd - 1) * N * N : nullptr, k0, k1, lane);
+                else if (cd >= 0 && cd <= nchunk - 1) {
+                    if constexpr (PACKED) dma_state(lds.s0, cd > 0 && !uniform_flag_u8(rs, cd) ? sbase + (size_t)(cd - 1) * N * N : nullptr, k0, k1, lane);
+                    else dma_state(lds.s0, cd > 0 ? sbase + (size_t)(cd - 1) * N * N : nullptr, k0, k1, lane);
+                }
             }
-            if (FULL || (ct >= 0 && ct <= nchunk - 1)) tail8(lds, ct & 1, qt, p, head_base + (size_t)ct * L * ts, lane_boff, c16, w, g, la);
+            if (FULL || (ct >= 0 && ct <= nchunk - 1)) {
+                if constexpr (PACKED) tail8(lds, ct & 1, qt, p, head_base + (size_t)ct * L * ts, lane_boff, c16, w, g, la, uniform_flag_u8(rs, ct) != 0);
+                else tail8(lds, ct & 1, qt, p, head_base + (size_t)ct * L * ts, lane_boff, c16, w, g, la);
+            }
             WKV_STAMP(0)
             if (SHIFT) { q2 = q1; q1 = q0; }
             TailQ& qn = SHIFT ? q0 : qt;
@@ -432,6 +464,10 @@ __global__ __launch_bounds__(768) void bwd_kernel_v8(BwdArgs p) {
                     acc = mfma32(xl8, y1, acc);
                     acc = mfma32(xh8, y2, acc);
                     dS1[jb] = acc;
+                }
+                if (PACKED && ci > 0 && uniform_flag_u8(rs, ci)) {      // nothing flows into the sample before
+#pragma unroll
+                    for (int jb = 0; jb < 4; ++jb) dS1[jb] = zero4();
                 }
             }
             WKV_STAMP(2)

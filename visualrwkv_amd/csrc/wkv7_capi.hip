@@ -88,9 +88,10 @@ int vrwkv_wkv7_set_backward_slice_limit(unsigned long long bytes) {
 int vrwkv_wkv7_last_variant(int backward) { return backward ? g_last_bwd.load() : g_last_fwd.load(); }
 
 int vrwkv_wkv7_resolve_variant(int kind, int B, int T, int H) {
-    if (check_common(B, T, H) != VRWKV_OK || kind < 0 || kind > 3) return VRWKV_EINVAL;
+    if (check_common(B, T, H) != VRWKV_OK || kind < 0 || kind > 5) return VRWKV_EINVAL;
     const long heads = (long)B * H;
-    if (kind == 1 || kind == 3) return resolve_bwd(heads, g_bwd_variant.load());
+    if (kind == 1 || kind == 3 || kind == 5) return resolve_bwd(heads, g_bwd_variant.load());
+    if (kind == 4) return 7;       // packed rows: wkv7_fwd_v4.h at every size
     return resolve_fwd(heads, g_fwd_variant.load(), kind == 2);
 }
 
@@ -226,6 +227,64 @@ int vrwkv_wkv7_backward_state_bf16(int B, int T, int H, const void* w, const voi
             rc2 = launch_lds(&wkv7v8::bwd_kernel_v8<false, false, true>, grid, dim3(768), sizeof(wkv7v8::LdsV8), st, p);
         else                 // the sequence-parallel kernel with one segment per head: it carries both state gradients already
             rc2 = launch_lds(&wkv7v5::bwd_kernel_v5<false, BWD_V5_MODE, true>, grid, dim3(512), sizeof(wkv7v5::LdsV5), st, p);
+        if (rc2) return rc2;
+    }
+    return VRWKV_OK;
+}
+
+int vrwkv_wkv7_forward_packed_bf16(int B, int T, int H, const void* w, const void* q, const void* k, const void* v,
+                                   const void* z, const void* a, void* y, const unsigned char* chunk_reset,
+                                   float* s_ckpt, float* sa, void* stream) {
+    int rc = check_common(B, T, H);
+    if (rc) return rc;
+    if (!w || !q || !k || !v || !z || !a || !y || (!s_ckpt != !sa)) return VRWKV_EINVAL;
+    if (misaligned(w) || misaligned(q) || misaligned(k) || misaligned(v) || misaligned(z) || misaligned(a) || misaligned(y) ||
+        (s_ckpt && misaligned(s_ckpt)) || (sa && misaligned(sa)))
+        return VRWKV_EALIGN;
+    wkv7::FwdArgs p{T, H, (const uint16_t*)w, (const uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v,
+                    (const uint16_t*)z, (const uint16_t*)a, (uint16_t*)y, s_ckpt, sa};
+    p.chunk_reset = chunk_reset;
+    // the full-row kernel at every size (it runs at any number of heads; the two-workgroups-per-head form of wkv7_fwd_v3.h has no resets)
+    g_last_fwd = 7;
+    const dim3 grid((unsigned)((long)B * H));
+    if (!chunk_reset) return launch_lds(&wkv7f4::fwd_kernel_v4<false>, grid, dim3(512), sizeof(wkv7f4::LdsF4), (hipStream_t)stream, p);
+    return launch_lds(&wkv7f4::fwd_kernel_v4<false, 1, true>, grid, dim3(512), sizeof(wkv7f4::LdsF4), (hipStream_t)stream, p);
+}
+
+int vrwkv_wkv7_backward_packed_bf16(int B, int T, int H, const void* w, const void* q, const void* k, const void* v,
+                                    const void* z, const void* a, const void* dy, const float* s, const float* sa,
+                                    const unsigned char* chunk_reset,
+                                    void* dw, void* dq, void* dk, void* dv, void* dz, void* da, void* stream) {
+    if (!chunk_reset) return vrwkv_wkv7_backward_bf16(B, T, H, w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da, stream);
+    int rc = check_common(B, T, H);
+    if (rc) return rc;
+    if (!w || !q || !k || !v || !z || !a || !dy || !s || !sa || !dw || !dq || !dk || !dv || !dz || !da) return VRWKV_EINVAL;
+    if (misaligned(w) || misaligned(q) || misaligned(k) || misaligned(v) || misaligned(z) || misaligned(a) ||
+        misaligned(dy) || misaligned(s) || misaligned(sa) || misaligned(dw) || misaligned(dq) || misaligned(dk) ||
+        misaligned(dv) || misaligned(dz) || misaligned(da))
+        return VRWKV_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    // kernel choice and batch slices of vrwkv_wkv7_backward_bf16; wkv7_bwd_v5.h has no resets: the caller runs the samples one by one then
+    const int var = resolve_bwd((long)B * H, g_bwd_variant.load());
+    if (var != 8 && var != 9) return VRWKV_ESHAPE;
+    const unsigned long long per_sample = (unsigned long long)T * H * 64ull * 4ull, limit = g_slice_limit.load();
+    int bmax = B;
+    if ((unsigned long long)B * per_sample >= limit) {
+        bmax = (int)((limit - 1) / per_sample);
+        if (bmax < 1) return VRWKV_ESHAPE;
+    }
+    g_last_bwd = var;
+    const size_t act = (size_t)T * H * 64, ckpt = (size_t)H * (T / VRWKV_CHUNK_LEN) * 64 * 64;      // elements per sample
+    for (int b0 = 0; b0 < B; b0 += bmax) {
+        const int nb = B - b0 < bmax ? B - b0 : bmax;
+        const size_t o = (size_t)b0 * act;
+        wkv7::BwdArgs p{T, H, (const uint16_t*)w + o, (const uint16_t*)q + o, (const uint16_t*)k + o, (const uint16_t*)v + o,
+                        (const uint16_t*)z + o, (const uint16_t*)a + o, (const uint16_t*)dy + o, s + (size_t)b0 * ckpt, sa + o,
+                        (uint16_t*)dw + o, (uint16_t*)dq + o, (uint16_t*)dk + o, (uint16_t*)dv + o, (uint16_t*)dz + o, (uint16_t*)da + o};
+        p.chunk_reset = chunk_reset + (size_t)b0 * (T / VRWKV_CHUNK_LEN);
+        const dim3 grid((unsigned)((long)nb * H));
+        const int rc2 = var == 9 ? launch_lds(&wkv7v8::bwd_kernel_v8<false, true, false, true>, grid, dim3(768), sizeof(wkv7v8::LdsV8), st, p)
+                                 : launch_lds(&wkv7v8::bwd_kernel_v8<false, false, false, true>, grid, dim3(768), sizeof(wkv7v8::LdsV8), st, p);
         if (rc2) return rc2;
     }
     return VRWKV_OK;

@@ -27,6 +27,7 @@
 namespace wkv7f4 {
 
 using wkv7::FwdArgs;
+using wkv7::uniform_flag_u8;
 using namespace wkv7c;       // N, L, mk8, split4, unpack4, ld8, st8, zero4, SF, WKV_STAMP*
 using namespace wkv7v5;      // IMG, HLI, img_off, hl_off, tix, LaneAddr, lane_addr, ld16, st16, mfma32, dot64, tiles_op
 using wkv7v7::DmaLane;
@@ -140,7 +141,12 @@ DEVFN f32x4 mm_f32_regs_image(f32x4 acc, f32x4 pt, const float (*M)[SF], int c16
     return acc;
 }
 
-template <bool PROF, int PRIO = 1>
+// PACKED (vrwkv_wkv7_forward_packed_bf16): a row holds several samples end to end, each a whole number of chunks.  S lives in the consumer
+// waves' registers across the chunk loop, so a sample boundary is one wave-uniform "S = 0" at the top of a flagged chunk (FwdArgs::chunk_reset,
+// a scalar load); the checkpoint of the chunk before was put into its output image a step earlier and is the state WITH the resets, which is
+// what a launch of that sample alone writes.  Everything else in a chunk step depends on the chunk's own rows only.  With PACKED off the
+// branch folds away.
+template <bool PROF, int PRIO = 1, bool PACKED = false>
 __global__ __launch_bounds__(512) void fwd_kernel_v4(FwdArgs p) {
     LdsF4& lds = *reinterpret_cast<LdsF4*>(dyn_lds());
     const int T = p.T, H = p.H;
@@ -210,6 +216,7 @@ __global__ __launch_bounds__(512) void fwd_kernel_v4(FwdArgs p) {
     float* psa = p.sa ? p.sa + head_base : nullptr;
     uint16_t* py = p.y + head_base;
     float* ps = p.s ? p.s + (size_t)bh * nchunk * N * N : nullptr;
+    const unsigned char* rs = PACKED ? p.chunk_reset + (size_t)(bh / H) * nchunk : nullptr;      // this row's flags
     // output images -> memory, 1 KB per instruction: checkpoint rows 16wt .. 16wt+15 (4 x 4 rows of 256 B), sa tokens 4wt .. 4wt+3,
     // y tokens 8wt .. 8wt+7 (waves 0, 1)
     const int sa_t = 4 * wt + (lane >> 4), y_t = 8 * (wt & 1) + (lane >> 3);
@@ -238,6 +245,10 @@ __global__ __launch_bounds__(512) void fwd_kernel_v4(FwdArgs p) {
         if (c > 0) {
             send(c - 1);
             lds_flag_add(&lds.cnt[2]);                  // (waits for the reads) the output images may be overwritten
+            if (PACKED && uniform_flag_u8(rs, c)) {     // a new sample starts here
+#pragma unroll
+                for (int jb = 0; jb < 4; ++jb) S[jb] = zero4();
+            }
         }
         bf16x8 bsh[2], bsl[2];
         tiles_op(S, bsh, bsl);

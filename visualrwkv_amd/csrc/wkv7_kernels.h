@@ -29,6 +29,8 @@ struct FwdArgs {
     // inference / stateful extensions honoured by fwd_kernel_v3 only (s and sa may then be null = not written):
     const float* s0 = nullptr;               // f32 (B,H,N,N) initial state S[i][j] (i = value row, j = key column)
     float* s_final = nullptr;                // f32 (B,H,N,N) state after the last token, same layout
+    // packed rows (fwd_kernel_v4<.., PACKED> only): (B, T/16) bytes; non-zero = this chunk starts a new sample, from S = 0
+    const unsigned char* chunk_reset = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -51,7 +53,24 @@ struct BwdArgs {
     const float* s0 = nullptr;                    // f32 (B,H,N,N)
     int want_grads = 0;                           // TPAR: 1 = a launch with ds_out and no ds_in still computes the six gradients (the state op);
                                                   // 0 = it is pass 1 of the sequence-parallel backward, whose gradients nobody reads (LITE)
+    // packed rows (bwd_kernel_v8<.., PACKED> only): (B, T/16) bytes, as FwdArgs::chunk_reset; `s` is then the walk WITH the resets
+    const unsigned char* chunk_reset = nullptr;
 };
+
+// One byte of a flag array at a wave-uniform index, as a scalar: the aligned dword that holds it comes through the constant address space
+// (s_load_dword: counted by lgkmcnt, so it neither waits for nor disturbs the vector-memory counter the memory roles of the kernels count
+// by hand), the byte is shifted out on the scalar unit.  The load covers the aligned 4-byte granule around the byte: up to 3 bytes before
+// the first / after the last flag of the array are read (never used), which every device allocation contains.
+DEVFN unsigned uniform_flag_u8(const unsigned char* flags, int idx) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned long long a = (unsigned long long)(uintptr_t)(flags + idx);
+    typedef __attribute__((address_space(4))) const unsigned* const_u32_ptr;
+    const unsigned word = *(const_u32_ptr)(a & ~3ull);
+    return __builtin_amdgcn_readfirstlane((word >> (8u * ((unsigned)a & 3u))) & 0xffu);
+#else
+    return flags[idx];
+#endif
+}
 
 
 }  // namespace wkv7

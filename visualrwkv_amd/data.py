@@ -109,15 +109,18 @@ def preprocess(conversations, tokenizer, has_image: bool, ctx_len: int, num_toke
     return dict(input_ids=input_ids, labels=targets, input_text=text)
 
 
-def build_sample(sample: Dict, tokenizer, ctx_len: int, num_token_per_image: int, pixel_values: Dict | None = None) -> Dict:
+def build_sample(sample: Dict, tokenizer, ctx_len: int, num_token_per_image: int, pixel_values: Dict | None = None,
+                 do_pad_to_max_length: bool = True) -> Dict:
     """What MyDataset.__getitem__ returns for one JSON record (dataset.py:196-246), given the already processed images
-    (`pixel_values`: tower name -> (n_images,3,H,W); None when the record has no image)."""
+    (`pixel_values`: tower name -> (n_images,3,H,W); None when the record has no image).  do_pad_to_max_length=False leaves ids and
+    labels at their own length (pack_batches pads and truncates them itself)."""
     if "image" in sample:
         n_img = 1 if isinstance(sample["image"], str) else len(sample["image"])
         conv = process_image_tokens_in_conversations(copy.deepcopy(sample["conversations"]), num_image_paths=n_img)
     else:
         conv = process_tokens_in_conversations(copy.deepcopy(sample["conversations"]))
-    out = preprocess(conv, tokenizer, has_image="image" in sample, ctx_len=ctx_len, num_token_per_image=num_token_per_image)
+    out = preprocess(conv, tokenizer, has_image="image" in sample, ctx_len=ctx_len, num_token_per_image=num_token_per_image,
+                     do_pad_to_max_length=do_pad_to_max_length)
     if "image" in sample:
         out["images"] = pixel_values if pixel_values is not None else {
             "dino": torch.zeros(n_img, 3, 448, 448), "siglip": torch.zeros(n_img, 3, 448, 448),
@@ -136,6 +139,94 @@ def multi_image_collate_fn(batch: Sequence[Dict]) -> Dict:
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Sample packing (not in the reference, which right-pads every sample to ctx_len: dataset.py:125-135).  Several samples lie end to
+# end in a row; the model restarts the WKV state and the token shift at every boundary (wkv7.PackedLayout), so each sample is
+# computed as if it had a row of its own.
+# ---------------------------------------------------------------------------------------------------------------
+PACK_CHUNK = 16          # wkv7.CHUNK_LEN: a segment is a whole number of WKV7 chunks
+
+
+def pack_batches(samples, micro_bsz: int, ctx_len: int, pad_token_id: int = 0):
+    """Generator over unpadded build_sample records (do_pad_to_max_length=False) -> packed batches of `micro_bsz` rows of `ctx_len` tokens.
+
+    Every sample is cut to ctx_len tokens as pad_to_max_len cuts it, padded to a multiple of 16 (id pad_token_id, label -100) and put
+    into the first row that still has room, in arrival order; the label of its first token becomes -100 (nothing in its own segment
+    predicts it).  The batch closes at the first sample that fits no row; that sample opens the next batch.  What is left of a row is
+    one pad-only segment.  A stream that ends mid-batch gives a last, partly filled batch.  Deterministic: no randomness, no dependence
+    on anything but the stream.
+
+    Yields the collated dict of multi_image_collate_fn / decode_collate_fn (images in (row, position) order, which is the order of the
+    image placeholders in input_ids.view(-1)) plus
+      seg_lens    per row, the token counts of its segments (multiples of 16 summing to ctx_len; a pad-only tail segment included)
+      sample_id   per row, the ids of its samples in order (pad-only segments have none)
+      n_samples   how many samples the batch holds."""
+    if ctx_len % PACK_CHUNK != 0 or ctx_len <= 0 or micro_bsz <= 0:
+        raise ValueError(f"pack_batches: ctx_len = {ctx_len} must be a positive multiple of {PACK_CHUNK} and micro_bsz = {micro_bsz} positive")
+    rows = [[] for _ in range(micro_bsz)]
+    free = [ctx_len] * micro_bsz
+
+    def close():
+        ids = torch.full((micro_bsz, ctx_len), pad_token_id, dtype=torch.long)
+        labels = torch.full((micro_bsz, ctx_len), IGNORE_INDEX, dtype=torch.long)
+        seg_lens, sample_ids, texts, flat = [], [], [], []
+        for r, row in enumerate(rows):
+            t0, lens = 0, []
+            for x, n in row:
+                m = len(x["input_ids"])
+                ids[r, t0:t0 + m] = x["input_ids"]
+                labels[r, t0:t0 + m] = x["labels"]
+                labels[r, t0] = IGNORE_INDEX
+                lens.append(n)
+                t0 += n
+            if t0 < ctx_len:
+                lens.append(ctx_len - t0)
+            seg_lens.append(lens)
+            sample_ids.append([str(x["sample_id"]) for x, _ in row])
+            texts.append([x.get("input_text") for x, _ in row])
+            flat.extend(x for x, _ in row)
+        out = dict(input_text=texts, input_ids=ids, labels=labels, sample_id=sample_ids, seg_lens=seg_lens, n_samples=len(flat))
+        if any("images_u8" in x or "images_missing" in x for x in flat):
+            out.update({k: v for k, v in decode_collate_fn([dict(x, input_ids=ids[0], labels=labels[0]) for x in flat]).items()
+                        if k in ("images_u8", "num_image_per_sample")})
+        elif any("images" in x for x in flat):
+            with_img = [x for x in flat if "images" in x]
+            images = {k: torch.cat([x["images"][k] for x in with_img], dim=0) for k in with_img[0]["images"]}
+            images["num_image_per_sample"] = [len(next(iter(x["images"].values()))) for x in with_img]
+            out["images"] = images
+        for r in range(micro_bsz):
+            rows[r] = []
+            free[r] = ctx_len
+        return out
+
+    for x in samples:
+        x = dict(x)
+        x["input_ids"], x["labels"] = x["input_ids"][:ctx_len], x["labels"][:ctx_len]
+        m = len(x["input_ids"])
+        if m == 0:
+            continue
+        n = -(-m // PACK_CHUNK) * PACK_CHUNK
+        r = next((i for i in range(micro_bsz) if free[i] >= n), None)
+        if r is None:
+            yield close()
+            r = 0
+        rows[r].append((x, n))
+        free[r] -= n
+    if any(rows):
+        yield close()
+
+
+class PackedBatches(torch.utils.data.IterableDataset):
+    """A MyDataset (built with pack=True) read in index order through pack_batches: what make_loader(..., pack=True) iterates."""
+
+    def __init__(self, dataset, micro_bsz: int):
+        self.dataset, self.micro_bsz = dataset, micro_bsz
+
+    def __iter__(self):
+        ds = self.dataset
+        return pack_batches((ds[i] for i in range(len(ds))), self.micro_bsz, ds.args.ctx_len)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Dataset, loader and device prefetcher (SURVEY.md 8f rank 4; VisualRWKV-v7/v7.00/src/dataset.py:167-246, train.py:219-222)
 #
 # The reference decodes AND transforms every image (three bicubic resizes, one to 1024 x 1024) in its single DataLoader
@@ -148,9 +239,10 @@ class MyDataset(torch.utils.data.Dataset):
     real_bsz, micro_bsz (the reference's names).  `global_rank`, `world_size` and `real_epoch` are attributes the trainer
     sets, as in the reference (train_callback).  decode_only=True (default) returns the decoded uint8 images under
     'images_u8' for the device transform; decode_only=False applies `image_processor` (a callable image -> dict of
-    (3,S,S) tensors, as args.image_processor of the reference) in the worker."""
+    (3,S,S) tensors, as args.image_processor of the reference) in the worker.  pack=True: samples come out unpadded, for pack_batches
+    (make_loader(..., pack=True)); every rank packs what it draws, so the number of samples per step then varies by rank."""
 
-    def __init__(self, args, decode_only: bool = True, image_processor=None):
+    def __init__(self, args, decode_only: bool = True, image_processor=None, pack: bool = False):
         import json
         from .dp import largest_3n_plus_2_prime
         self.args = args
@@ -163,6 +255,7 @@ class MyDataset(torch.utils.data.Dataset):
         self.samples_per_epoch = args.epoch_steps * args.real_bsz
         self.decode_only = decode_only
         self.image_processor = image_processor
+        self.pack = pack
         self.global_rank, self.world_size, self.real_epoch = 0, 1, 0
 
     def __len__(self):
@@ -191,7 +284,8 @@ class MyDataset(torch.utils.data.Dataset):
                     pixel_values = {k: torch.stack([p[k] for p in per], dim=0) for k in per[0]}
             except Exception:                                    # unreadable image: zero tensors, as the reference (dataset.py:213-215)
                 images_u8, pixel_values = None, None
-        out = build_sample(sample, self.tokenizer, self.args.ctx_len, self.args.num_token_per_image, pixel_values)
+        out = build_sample(sample, self.tokenizer, self.args.ctx_len, self.args.num_token_per_image, pixel_values,
+                           do_pad_to_max_length=not self.pack)
         if "image" in sample and self.decode_only:
             if images_u8 is not None:
                 del out["images"]
@@ -217,9 +311,19 @@ def decode_collate_fn(batch: Sequence[Dict]) -> Dict:
                 sample_id=[str(x["sample_id"]) for x in batch])
 
 
-def make_loader(dataset: "MyDataset", micro_bsz: int, num_workers: int = 4):
+def make_loader(dataset: "MyDataset", micro_bsz: int, num_workers: int = 4, pack: bool = False):
     """train.py:219-222 with decode-only workers: shuffle=False (the dataset does the rank-strided sampling), drop_last,
-    pinned memory; more than the reference's single worker is safe because __getitem__ depends on idx only."""
+    pinned memory; more than the reference's single worker is safe because __getitem__ depends on idx only.
+    pack=True (the dataset built with pack=True as well): batches come from pack_batches over the same sample stream, read by at most
+    one worker so that the order, and with it the packing, stays that of the stream.  One pass then yields about
+    len(dataset) / micro_bsz / (samples per row) batches -- a count that depends on the lengths drawn, so it differs from rank to rank --
+    and the last one may be partly filled (no drop_last).  A multi-rank trainer drives this loader by step count, every rank the same
+    number of steps (re-iterating it as needed), not to exhaustion, and keys its LR schedule to those steps."""
+    if pack:
+        if not getattr(dataset, "pack", False):
+            raise ValueError("make_loader(pack=True) needs a MyDataset built with pack=True (unpadded samples)")
+        return torch.utils.data.DataLoader(PackedBatches(dataset, micro_bsz), batch_size=None, shuffle=False,
+                                           pin_memory=torch.cuda.is_available(), num_workers=min(num_workers, 1))
     return torch.utils.data.DataLoader(dataset, collate_fn=decode_collate_fn if dataset.decode_only else multi_image_collate_fn,
                                        shuffle=False, pin_memory=torch.cuda.is_available(), batch_size=micro_bsz,
                                        num_workers=num_workers, persistent_workers=False, drop_last=True)
@@ -239,6 +343,9 @@ class DevicePrefetcher:
         nb = self.device.type == "cuda"
         out = {"input_ids": batch["input_ids"].to(self.device, non_blocking=nb), "labels": batch["labels"].to(self.device, non_blocking=nb),
                "sample_id": batch["sample_id"], "input_text": batch.get("input_text")}
+        for k in ("seg_lens", "n_samples"):                      # packed batches (pack_batches): host lists the model builds its layout from
+            if k in batch:
+                out[k] = batch[k]
         if "images_u8" in batch:
             if batch["images_u8"]:
                 per_tower = {t: [] for t in self.towers}

@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from . import gemm_tuning, hip_lib
-from .wkv7 import RUN_CUDA_RWKV7g, RUN_CUDA_RWKV7g_state
+from .wkv7 import RUN_CUDA_RWKV7g, RUN_CUDA_RWKV7g_packed, RUN_CUDA_RWKV7g_state
 
 
 def _stream(t):
@@ -626,10 +626,12 @@ def add_ln_infer(x, delta, dscale, ln):
 class _AddLnMix(torch.autograd.Function):
     """(xn, out_0 .. out_{M-1}) = (x + delta, lerps of the token-shifted LayerNorm(x + delta)): `_AddLN` followed by `_Mix` in one
     kernel each way (csrc/ln_fused.hip: ln_mix_*): the LayerNorm output is never written.  M = 1 (channel-mix) or 6 (time-mix);
-    dup3: a 7th output aliasing output 3 (x_v) for its second consumer, as `_MixDup3`.  delta may be None (first block)."""
+    dup3: a 7th output aliasing output 3 (x_v) for its second consumer, as `_MixDup3`.  delta may be None (first block).
+    first: None, or the (B*T) uint8 marks of a wkv7.PackedLayout (rows that hold several samples end to end): the _packed entries then
+    shift zeros into every sample's first token and send no gradient from it to the row before."""
 
     @staticmethod
-    def forward(ctx, x, delta, w, b, eps, dup3, *mus):
+    def forward(ctx, x, delta, w, b, eps, dup3, first, *mus):
         B, T, C = x.shape
         M = len(mus)
         x = x.contiguous()
@@ -642,10 +644,13 @@ class _AddLnMix(torch.autograd.Function):
         outs = [torch.empty_like(x) for _ in mus]
         mean = torch.empty(ntok, dtype=torch.float32, device=x.device)
         rstd = torch.empty(ntok, dtype=torch.float32, device=x.device)
-        rc = hip_lib.load().vrwkv_ln_mix_fwd_bf16(ntok, T, C, float(eps), M, x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
-                                                  _ptr_array(mus_c), xn.data_ptr() if delta is not None else 0, _ptr_array(outs),
-                                                  mean.data_ptr(), rstd.data_ptr(), _stream(x))
-        hip_lib.check(rc, "vrwkv_ln_mix_fwd_bf16")
+        if first is not None and (first.dtype != torch.uint8 or first.numel() != ntok or first.device != x.device or not first.is_contiguous()):
+            raise ValueError(f"add_ln_mix: `first` must be a contiguous uint8 tensor of {ntok} marks on {x.device}")
+        rc = hip_lib.load().vrwkv_ln_mix_fwd_packed_bf16(ntok, T, C, float(eps), M, x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
+                                                         _ptr_array(mus_c), xn.data_ptr() if delta is not None else 0, _ptr_array(outs),
+                                                         mean.data_ptr(), rstd.data_ptr(), _p(first), _stream(x))
+        hip_lib.check(rc, "vrwkv_ln_mix_fwd_packed_bf16")
+        ctx.first = first
         ctx.save_for_backward(xn, mean, rstd, wc, bc, *mus_c)
         ctx.has_delta = delta is not None
         ctx.mu_shapes = [m.shape for m in mus]
@@ -669,30 +674,36 @@ class _AddLnMix(torch.autograd.Function):
         lib = hip_lib.load()
         if M == 1:
             ws = torch.empty(lib.vrwkv_ln_mix_ws_floats(ntok, C, M), dtype=torch.float32, device=xn.device)
-            rc = lib.vrwkv_ln_mix_bwd_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
-                                           _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), _p(d_xn), dx.data_ptr(), dwb.data_ptr(),
-                                           dmu.data_ptr(), ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, "vrwkv_ln_mix_bwd_bf16")
+            rc = lib.vrwkv_ln_mix_bwd_packed_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
+                                                  _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), _p(d_xn), _p(ctx.first), dx.data_ptr(),
+                                                  dwb.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
+            hip_lib.check(rc, "vrwkv_ln_mix_bwd_packed_bf16")
         else:       # six lerps: their backward with the LayerNorm output recomputed in place of a stored one, then the LayerNorm's
             dy = torch.empty_like(xn)
             ws = _ws(ntok, C, M, xn.device)
-            rc = lib.vrwkv_mix_bwd_ln_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
-                                           _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), dy.data_ptr(), dmu.data_ptr(),
-                                           ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, "vrwkv_mix_bwd_ln_bf16")
+            rc = lib.vrwkv_mix_bwd_ln_packed_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
+                                                  _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), _p(ctx.first), dy.data_ptr(),
+                                                  dmu.data_ptr(), ws.data_ptr(), _stream(xn))
+            hip_lib.check(rc, "vrwkv_mix_bwd_ln_packed_bf16")
             ws = torch.empty(lib.vrwkv_add_ln_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
             rc = lib.vrwkv_add_ln_bwd_bf16(ntok, C, dy.data_ptr(), _p(d_xn), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                            wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
             hip_lib.check(rc, "vrwkv_add_ln_bwd_bf16")
         dwb = dwb.to(wc.dtype)
         dmu = dmu.to(xn.dtype)
-        return (dx, (dx if ctx.has_delta else None), dwb[0], dwb[1], None, None, *[dmu[i].view(sh) for i, sh in enumerate(ctx.mu_shapes)])
+        return (dx, (dx if ctx.has_delta else None), dwb[0], dwb[1], None, None, None, *[dmu[i].view(sh) for i, sh in enumerate(ctx.mu_shapes)])
 
 
-def add_ln_mix(x, delta, ln, mus, dup3=False):
-    """Returns (x + delta, [lerp outputs]) -- see `_AddLnMix`."""
-    xn, *outs = _AddLnMix.apply(x, delta, ln.weight, ln.bias, ln.eps, dup3, *mus)
+def add_ln_mix(x, delta, ln, mus, dup3=False, first=None):
+    """Returns (x + delta, [lerp outputs]) -- see `_AddLnMix`.  first: the marks of a wkv7.PackedLayout (layout.first) for packed rows."""
+    xn, *outs = _AddLnMix.apply(x, delta, ln.weight, ln.bias, ln.eps, dup3, first, *mus)
     return xn, outs
+
+
+def packed_supported(x):
+    """May a packed batch (wkv7.PackedLayout) take blocks_forward?  It needs both shifts inside the ln_mix kernels: the two-kernel shift
+    (VRWKV_LN_MIX=0 / VRWKV_LN_MIX_TMIX=0, vrwkv_mix_fwd / _bwd) finds a first token as n % T == 0 only; the caller runs the unfused Blocks then."""
+    return ln_mix_supported(x) and LN_MIX_TMIX
 
 
 LN_MIX = os.environ.get("VRWKV_LN_MIX", "1") != "0"              # A/B switch: 0 = add_ln and mix as two kernels
@@ -707,26 +718,30 @@ def add_ln_supported(x):
     return x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 64 == 0 and x.shape[-1] <= 8192
 
 
-def _block_segment(block, x, delta, v_first, selective=False):
+def _block_segment(block, x, delta, v_first, selective=False, layout=None):
     """One Block on the (x, pending delta) residual stream: returns (x + delta, ffn output still to be added, v_first).
-    selective: the selective-recompute mode of blocks_forward (WKV7 by-products and relu(h)^2 are re-formed in the backward)."""
+    selective: the selective-recompute mode of blocks_forward (WKV7 by-products and relu(h)^2 are re-formed in the backward).
+    layout: a wkv7.PackedLayout -- both token shifts and the WKV7 state restart at every sample of a row (packed_supported(x) must hold)."""
     att, ffn = block.att, block.ffn
     fuse = ln_mix_supported(x) and getattr(att.args, "fused", False)
+    first = layout.first if layout is not None else None
+    if layout is not None and not (fuse and LN_MIX_TMIX):
+        raise NotImplementedError("packed rows need the fused ln_mix kernels for both token shifts (fused.packed_supported)")
     if fuse and LN_MIX_TMIX:
         dup3 = torch.is_grad_enabled() and GRAD_ALIAS and att.layer_id > 0
-        x, mixed = add_ln_mix(x, delta, block.ln1, (att.x_r, att.x_w, att.x_k, att.x_v, att.x_a, att.x_g), dup3)
-        att_out, v_first = tmix_from_mixed(att, mixed, v_first, recompute_state=selective)
+        x, mixed = add_ln_mix(x, delta, block.ln1, (att.x_r, att.x_w, att.x_k, att.x_v, att.x_a, att.x_g), dup3, first)
+        att_out, v_first = tmix_from_mixed(att, mixed, v_first, recompute_state=selective, layout=layout)
     else:
         x, h = add_ln(x, delta, block.ln1)
         att_out, v_first = tmix_forward(att, h, v_first, recompute_state=selective) if getattr(att.args, "fused", False) else att(h, v_first)
     if fuse:            # ln2 + the channel-mix lerp in one kernel: the LayerNorm output is never materialised
-        x, (k,) = add_ln_mix(x, att_out, block.ln2, (ffn.x_k,))
+        x, (k,) = add_ln_mix(x, att_out, block.ln2, (ffn.x_k,), False, first)
         return x, cmix_from_mixed(ffn, k, recompute_relusq=selective), v_first
     x, h = add_ln(x, att_out, block.ln2)
     return x, ffn(h), v_first
 
 
-def blocks_forward(rwkv, x, grad_cp=0):
+def blocks_forward(rwkv, x, grad_cp=0, layout=None):
     """All Blocks + ln_out with the residual adds fused into the LayerNorms (same math as Block.forward chained,
     src/model.py:247-254,313-318): the residual stream is carried as (x, pending delta).
     grad_cp (the reference's memory-saving switch, src/model.py:318-319: deepspeed.checkpointing.checkpoint per block):
@@ -737,7 +752,8 @@ def blocks_forward(rwkv, x, grad_cp=0):
          large -- the WKV7 chunk checkpoints `s` and `sa` (10 of the ~40 activation tensors of a layer: the backward re-runs the forward kernel)
          and relu(h)^2 of the channel-mix (4 of them: one streaming kernel) -- about a third of the activation memory for ~1 ms per layer.
     (Rounds 4-5 had 1 and 2 the other way round; a trainer configured for the reference's `--grad_cp 1` must not get the mode that needs 3x
-    the memory.)"""
+    the memory.)
+    layout: a wkv7.PackedLayout when the rows hold several samples end to end; every mode passes it to every Block."""
     grad_cp = int(grad_cp) if torch.is_grad_enabled() else 0
     if grad_cp not in (0, 1, 2):
         raise ValueError(f"grad_cp = {grad_cp}: 0 (keep everything), 1 (re-compute every block, the reference's recipe) or 2 (selective recompute)")
@@ -747,9 +763,9 @@ def blocks_forward(rwkv, x, grad_cp=0):
     for block in rwkv.blocks:
         if grad_cp == 1:
             from torch.utils.checkpoint import checkpoint
-            x, delta, v_first = checkpoint(_block_segment, block, x, delta, v_first, use_reentrant=False)
+            x, delta, v_first = checkpoint(_block_segment, block, x, delta, v_first, False, layout, use_reentrant=False)
         else:
-            x, delta, v_first = _block_segment(block, x, delta, v_first, grad_cp == 2)
+            x, delta, v_first = _block_segment(block, x, delta, v_first, grad_cp == 2, layout)
     _, h = add_ln(x, delta, rwkv.ln_out)
     return h
 
@@ -815,16 +831,28 @@ class HeadPlan:
     """The labelled rows of one batch, formed at the start of training_step from the labels alone: the shifted labels and per-row loss
     weights of _FusedCE, and the count of labelled rows copied to pinned host memory behind an event -- by the head's backward the copy has
     long landed, so reading it waits for nothing (no device-wide synchronisation in the step).  Rows are those of the hidden state left-padded
-    by `pad` rows per sample (RWKV.forward_features): pad rows carry no label and get no gradient.  Nothing is cached across batches."""
+    by `pad` rows per sample (RWKV.forward_features): pad rows carry no label and get no gradient.  Nothing is cached across batches.
+    layout (a wkv7.PackedLayout; pad is 0 then): "sample" means segment of a packed row -- the last row of a segment has no target, and a
+    labelled row weighs 1 / (valid labels of its segment * layout.n_samples)."""
 
-    def __init__(self, targets, pad, ignore_index=-100):
+    def __init__(self, targets, pad, ignore_index=-100, layout=None):
         B, T = targets.shape
         dev = targets.device
         labels = torch.full((B, T), ignore_index, dtype=torch.long, device=dev)
         labels[:, :-1] = targets[:, 1:]                       # row (b,t) predicts token t+1; the last row has no target
         labels = torch.where(labels == ignore_index, torch.full_like(labels, -100), labels)
-        valid = (labels >= 0).sum(1).clamp(min=1)
-        self.w = ((labels >= 0).float() / (valid.float().unsqueeze(1) * B)).view(B * T)      # _FusedCE's d loss / d row_loss
+        if layout is None:
+            valid = (labels >= 0).sum(1).clamp(min=1)
+            self.w = ((labels >= 0).float() / (valid.float().unsqueeze(1) * B)).view(B * T)      # _FusedCE's d loss / d row_loss
+        else:
+            if pad != 0:
+                raise ValueError("HeadPlan: packed rows are whole chunks, pad must be 0")
+            layout.check(B, T, dev)
+            labels[:, :-1] = labels[:, :-1].masked_fill(layout.first.view(B, T)[:, 1:].bool(), -100)      # the next token opens another sample
+            lab = (labels >= 0).float().view(-1)
+            seg = layout.seg_id.view(-1).long()
+            valid = torch.zeros(layout.n_segments, dtype=torch.float32, device=dev).index_add_(0, seg, lab).clamp_(min=1)
+            self.w = lab / (valid[seg] * layout.n_samples)
         self.B, self.T, self.pad = B, T, pad
         Tp = T + pad
         lab_p = torch.full((B, Tp), -100, dtype=torch.long, device=dev)
@@ -1090,8 +1118,11 @@ def blocks6_forward(rwkv, x, wkv=None, grad_cp=False):
     return h
 
 
-def tmix_forward(m, x, v_first, recompute_state=False):
-    """RWKV_Tmix_x070.forward (src/model.py:163-195) with the glue fused; `m` is the module."""
+def tmix_forward(m, x, v_first, recompute_state=False, layout=None):
+    """RWKV_Tmix_x070.forward (src/model.py:163-195) with the glue fused; `m` is the module.  Its own shift kernel (vrwkv_mix_fwd) knows no
+    sample boundaries inside a row: packed rows come through add_ln_mix + tmix_from_mixed (blocks_forward)."""
+    if layout is not None:
+        raise NotImplementedError("tmix_forward: packed rows take their token shift in add_ln_mix (fused.blocks_forward), not in the two-kernel path")
     train = torch.is_grad_enabled()
     if train and GRAD_ALIAS and m.layer_id > 0:          # x_v, k2, v2 have two consumers each: aliases keep their gradients apart until the
         mixed = mix_dup3(x, m.x_r, m.x_w, m.x_k, m.x_v, m.x_a, m.x_g)      # backward kernels sum them
@@ -1100,8 +1131,9 @@ def tmix_forward(m, x, v_first, recompute_state=False):
     return tmix_from_mixed(m, mixed, v_first, recompute_state)
 
 
-def tmix_from_mixed(m, mixed, v_first, recompute_state=False):
-    """The time-mix after its token shift: `mixed` = (xr, xw, xk, xv, xa, xg[, alias of xv for its second consumer])."""
+def tmix_from_mixed(m, mixed, v_first, recompute_state=False, layout=None):
+    """The time-mix after its token shift: `mixed` = (xr, xw, xk, xv, xa, xg[, alias of xv for its second consumer]).
+    layout: a wkv7.PackedLayout -- the WKV7 op restarts its state at every sample of a row (one packed launch each way)."""
     xr, xw, xk, xv, xa, xg = mixed[:6]
     xv_b = mixed[6] if len(mixed) > 6 else xv
     mm = lora_mm if torch.is_grad_enabled() and LORA_WGRAD else torch.matmul     # training: skinny weight-gradient kernel in the backward
@@ -1122,7 +1154,11 @@ def tmix_from_mixed(m, mixed, v_first, recompute_state=False):
             k2, v2, z, b, k2_b, v2_b = kva(k, v, v_first, vl, al, m.k_k, m.k_a, m.a0, m.v0, True)
         if not GRAD_ALIAS:
             k2_b, v2_b = k2, v2
-    if getattr(m, "time_state", None) is not None:      # state tuning: the recurrence starts from the layer's learnable state
+    if layout is not None:
+        if getattr(m, "time_state", None) is not None:
+            raise NotImplementedError("packed rows together with a tuned state: every segment would have to start from it")
+        y = RUN_CUDA_RWKV7g_packed(r, w, k2, v2, z, b, layout, recompute_state=recompute_state)
+    elif getattr(m, "time_state", None) is not None:      # state tuning: the recurrence starts from the layer's learnable state
         y, _ = RUN_CUDA_RWKV7g_state(r, w, k2, v2, z, b, m.wkv_initial_state(), recompute_state=recompute_state)
     else:
         y = RUN_CUDA_RWKV7g(r, w, k2, v2, z, b, recompute_state=recompute_state)

@@ -20,6 +20,8 @@ PROTOTYPES = {
     "vrwkv_wkv7_backward_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 16),
     "vrwkv_wkv7_backward_segments_bf16": (_c_int, [_c_int] * 4 + [_c_void_p] * 18),
     "vrwkv_wkv7_backward_state_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 19),
+    "vrwkv_wkv7_forward_packed_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 11),
+    "vrwkv_wkv7_backward_packed_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 17),
     "vrwkv_wkv7_forward_host": (_c_int, [_c_int] * 4 + [_c_void_p] * 9 + [_c_int]),
     "vrwkv_wkv7_backward_host": (_c_int, [_c_int] * 4 + [_c_void_p] * 15 + [_c_int]),
     "vrwkv_wkv6_ckpt_floats": (_c_long, [_c_int] * 3),
@@ -34,6 +36,9 @@ PROTOTYPES = {
     "vrwkv_ln_mix_fwd_bf16": (_c_int, [_c_long, _c_int, _c_int, ctypes.c_float, _c_int] + [_c_void_p] * 10),
     "vrwkv_ln_mix_bwd_bf16": (_c_int, [_c_long, _c_int, _c_int, _c_int] + [_c_void_p] * 14),
     "vrwkv_mix_bwd_ln_bf16": (_c_int, [_c_long, _c_int, _c_int, _c_int] + [_c_void_p] * 12),
+    "vrwkv_ln_mix_fwd_packed_bf16": (_c_int, [_c_long, _c_int, _c_int, ctypes.c_float, _c_int] + [_c_void_p] * 11),
+    "vrwkv_ln_mix_bwd_packed_bf16": (_c_int, [_c_long, _c_int, _c_int, _c_int] + [_c_void_p] * 15),
+    "vrwkv_mix_bwd_ln_packed_bf16": (_c_int, [_c_long, _c_int, _c_int, _c_int] + [_c_void_p] * 13),
     "vrwkv_ce_fwd_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 7),
     "vrwkv_ce_bwd_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 6 + [_c_float] + [_c_void_p] * 2),
     "vrwkv_ce_bwd_rows_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 6 + [_c_float] + [_c_void_p] * 3),

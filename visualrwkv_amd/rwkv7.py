@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 from torch.nn import functional as F
 
-from .wkv7 import CHUNK_LEN, RUN_CUDA_RWKV7g, RUN_CUDA_RWKV7g_state
+from .wkv7 import CHUNK_LEN, RUN_CUDA_RWKV7g, RUN_CUDA_RWKV7g_packed, RUN_CUDA_RWKV7g_state
 
 STOP_TOKEN_INDEX = 261        # src/dataset.py:20  ("\n\n"), used to left-pad to a multiple of CHUNK_LEN
 IGNORE_INDEX = -100           # src/dataset.py:17
@@ -35,9 +35,13 @@ def _ortho(rows: int, cols: int, scale: float) -> torch.Tensor:
     return w
 
 
-def time_shift(x: torch.Tensor) -> torch.Tensor:
-    """x_{t-1} with zeros at t = 0 of every sample (nn.ZeroPad2d((0,0,1,-1)), src/model.py:149)."""
-    return F.pad(x, (0, 0, 1, -1))
+def time_shift(x: torch.Tensor, layout=None) -> torch.Tensor:
+    """x_{t-1} with zeros at t = 0 of every sample (nn.ZeroPad2d((0,0,1,-1)), src/model.py:149).  With a wkv7.PackedLayout the first token
+    of every segment of a packed row reads zeros too, and no gradient goes from it to the token before."""
+    xs = F.pad(x, (0, 0, 1, -1))
+    if layout is not None:
+        xs = xs.masked_fill(layout.first.view(x.shape[0], x.shape[1], 1).bool(), 0)
+    return xs
 
 
 class RWKV_Tmix_x070(nn.Module):
@@ -111,18 +115,21 @@ class RWKV_Tmix_x070(nn.Module):
             return None
         return ts if ts.dtype == torch.float64 else ts.float()
 
-    def forward(self, x, v_first, state=None):
-        """`state` (an RWKV7State; inference: no gradient flows through it) carries the previous token and the WKV state across calls."""
+    def forward(self, x, v_first, state=None, layout=None):
+        """`state` (an RWKV7State; inference: no gradient flows through it) carries the previous token and the WKV state across calls.
+        `layout` (a wkv7.PackedLayout; training on packed rows): the shift and the WKV state restart at every segment."""
         B, T, C = x.size()
         H = self.n_head
-        if getattr(self.args, "fused", False) and x.is_cuda:
+        if layout is not None and (state is not None or getattr(self, "time_state", None) is not None):
+            raise NotImplementedError("packed rows together with a carried or tuned state: every segment would have to start from it")
+        if getattr(self.args, "fused", False) and x.is_cuda and layout is None:
             from . import fused
             if state is None:
                 return fused.tmix_forward(self, x, v_first)
             if not torch.is_grad_enabled() and x.dtype == torch.bfloat16:
                 return fused.tmix_forward_stateful(self, x, v_first, state)
         if state is None:
-            xx = time_shift(x) - x
+            xx = time_shift(x, layout) - x
         else:
             xx = torch.cat((state.att_x[self.layer_id].unsqueeze(1), x[:, :-1]), dim=1) - x
             state.att_x[self.layer_id].copy_(x[:, -1])          # in place: the state tensors are stable addresses (HIP graphs)
@@ -148,7 +155,9 @@ class RWKV_Tmix_x070(nn.Module):
         kk = F.normalize(kk.view(B, T, H, -1), dim=-1, p=2.0).view(B, T, C)
         k = k * (1 + (a - 1) * self.k_a)
 
-        if state is None and getattr(self, "time_state", None) is not None:
+        if layout is not None:
+            x = RUN_CUDA_RWKV7g_packed(r, w, k, v, -kk, kk * a, layout)
+        elif state is None and getattr(self, "time_state", None) is not None:
             x, _ = RUN_CUDA_RWKV7g_state(r, w, k, v, -kk, kk * a, self.wkv_initial_state())
         elif state is None:
             x = RUN_CUDA_RWKV7g(r, w, k, v, -kk, kk * a)
@@ -178,15 +187,15 @@ class RWKV_CMix_x070(nn.Module):
         self.key.weight.data.uniform_(-0.5 / (C ** 0.5), 0.5 / (C ** 0.5))
         self.value.weight.data.zero_()
 
-    def forward(self, x, state=None):
-        if getattr(self.args, "fused", False) and x.is_cuda:
+    def forward(self, x, state=None, layout=None):
+        if getattr(self.args, "fused", False) and x.is_cuda and layout is None:
             from . import fused
             if state is None:
                 return fused.cmix_forward(self, x)
             if not torch.is_grad_enabled() and x.dtype == torch.bfloat16:
                 return fused.cmix_forward_stateful(self, x, state)
         if state is None:
-            xx = time_shift(x) - x
+            xx = time_shift(x, layout) - x
         else:
             xx = torch.cat((state.ffn_x[self.layer_id].unsqueeze(1), x[:, :-1]), dim=1) - x
             state.ffn_x[self.layer_id].copy_(x[:, -1])
@@ -209,10 +218,14 @@ class Block(nn.Module):
         self.att = RWKV_Tmix_x070(args, layer_id)
         self.ffn = RWKV_CMix_x070(args, layer_id)
 
-    def forward(self, x, v_first, state=None):
+    def forward(self, x, v_first, state=None, layout=None):
         if self.layer_id == 0:
             x = self.ln0(x)
-        if state is None:
+        if layout is not None:
+            xx, v_first = self.att(self.ln1(x), v_first, None, layout)
+            x = x + xx
+            x = x + self.ffn(self.ln2(x), None, layout)
+        elif state is None:
             xx, v_first = self.att(self.ln1(x), v_first)
             x = x + xx
             x = x + self.ffn(self.ln2(x))
@@ -309,14 +322,34 @@ class RWKV(nn.Module):
     def unpad(self, x, num_tokens_to_pad):
         return x[:, num_tokens_to_pad:] if num_tokens_to_pad > 0 else x
 
-    def forward_features(self, x):
-        """Everything up to (not including) the head; returns (hidden, num_tokens_to_pad)."""
+    def forward_features(self, x, layout=None):
+        """Everything up to (not including) the head; returns (hidden, num_tokens_to_pad).  layout: a wkv7.PackedLayout for packed rows
+        (T is then a multiple of CHUNK_LEN by construction: no left pad)."""
         args = self.args
+        if layout is not None:
+            layout.check(x.size(0), x.size(1), x.device)
+            if getattr(args, "state_tune", 0):
+                raise NotImplementedError("packed rows together with args.state_tune: every segment would have to start from time_state")
         rem = x.size(1) % CHUNK_LEN
         num_tokens_to_pad = CHUNK_LEN - rem if rem != 0 else 0
         x = self.pad_left(x, num_tokens_to_pad)
         if args.dropout > 0:
             x = self.drop0(x)
+        if layout is not None and getattr(args, "fused", False):
+            from . import fused
+            if fused.packed_supported(x):
+                return fused.blocks_forward(self, x, grad_cp=int(args.grad_cp) if torch.is_grad_enabled() else 0, layout=layout), num_tokens_to_pad
+        if layout is not None:
+            # the unfused Blocks (masked shift in PyTorch, the WKV7 op packed on device tensors): CPU tensors, args.fused off, or the
+            # two-kernel shift selected (VRWKV_LN_MIX=0), whose kernels know no sample boundaries inside a row
+            v_first = torch.empty_like(x)
+            for block in self.blocks:
+                if args.grad_cp >= 1 and torch.is_grad_enabled():
+                    from torch.utils.checkpoint import checkpoint
+                    x, v_first = checkpoint(block, x, v_first, None, layout, use_reentrant=False)
+                else:
+                    x, v_first = block(x, v_first, None, layout)
+            return self.ln_out(x), num_tokens_to_pad
         if getattr(args, "fused", False):
             from . import fused
             if fused.add_ln_supported(x):
@@ -330,11 +363,12 @@ class RWKV(nn.Module):
                 x, v_first = block(x, v_first)
         return self.ln_out(x), num_tokens_to_pad
 
-    def forward(self, x, hidden_only=False):
-        """Logits (B, T, V); hidden_only: forward_features(x) instead (through the module call, so that forward pre-hooks run)."""
+    def forward(self, x, hidden_only=False, layout=None):
+        """Logits (B, T, V); hidden_only: forward_features(x) instead (through the module call, so that forward pre-hooks run).
+        layout: a wkv7.PackedLayout when the rows hold several samples end to end."""
         if hidden_only:
-            return self.forward_features(x)
-        x, num_tokens_to_pad = self.forward_features(x)
+            return self.forward_features(x, layout)
+        x, num_tokens_to_pad = self.forward_features(x, layout)
         if x.is_cuda and getattr(self.args, "fused", False):
             from . import fused
             x = fused.linear(self.head, x)              # input gradient in the forward GEMMs' layout

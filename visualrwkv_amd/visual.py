@@ -165,16 +165,39 @@ class VisualRWKV(nn.Module):
         input_embeds = input_embeds.masked_scatter(selected[:, None], image_features.to(input_embeds.dtype))
         return input_embeds.view(B, Ln, D), samples["labels"]
 
+    @staticmethod
+    def packed_layout(samples, device):
+        """The wkv7.PackedLayout of a batch from data.pack_batches (it carries `seg_lens`), or None for an ordinary padded batch."""
+        if samples.get("seg_lens") is None:
+            return None
+        from .wkv7 import PackedLayout
+        return PackedLayout(samples["seg_lens"], samples["input_ids"].shape[1], device, n_samples=samples.get("n_samples"))
+
     def forward(self, samples):
         x, targets = self.preparing_embedding(samples)
+        layout = self.packed_layout(samples, x.device)
+        if layout is not None:
+            return self.rwkv(x, layout=layout), targets
         return self.rwkv(x), targets
 
     @staticmethod
-    def loss_from_logits(logits, targets):
+    def loss_from_logits(logits, targets, layout=None):
         """Shifted CE, summed per sample over valid labels / max(valid,1), batch mean, wrapped in L2Wrap
-        (src/model.py:418-434)."""
+        (src/model.py:418-434).  With a layout "sample" means segment of a packed row: the last row of a segment has no target, the mean
+        runs over layout.n_samples; L2Wrap keeps the reference's formula on the packed (B, T) logits."""
         shift_logits = logits[..., :-1, :].contiguous()
         shift_labels = targets[..., 1:].contiguous()
+        if layout is not None:
+            Bp, Tp = targets.shape
+            shift_labels = shift_labels.masked_fill(layout.first.view(Bp, Tp)[:, 1:].bool(), IGNORE_INDEX)
+            seg = layout.seg_id[:, 1:].reshape(-1).long()        # the segment of the token a row predicts
+            loss = F.cross_entropy(shift_logits.view(-1, shift_logits.size(-1)), shift_labels.view(-1),
+                                   ignore_index=IGNORE_INDEX, reduction="none")
+            total = torch.zeros(layout.n_segments, dtype=loss.dtype, device=loss.device).index_add_(0, seg, loss)
+            valid = torch.zeros(layout.n_segments, dtype=loss.dtype, device=loss.device).index_add_(
+                0, seg, (shift_labels.view(-1) != IGNORE_INDEX).to(loss.dtype))
+            loss = (total / valid.clamp_min(1)).sum() / layout.n_samples
+            return L2Wrap.apply(loss, logits)
         valid = (shift_labels != IGNORE_INDEX).sum(1)
         valid = torch.max(valid, torch.ones_like(valid))
         loss = F.cross_entropy(shift_logits.view(-1, shift_logits.size(-1)), shift_labels.view(-1),
@@ -184,6 +207,20 @@ class VisualRWKV(nn.Module):
 
     def training_step(self, batch, batch_idx=0):
         logits = None
+        if batch.get("seg_lens") is not None:            # a packed batch (data.pack_batches): per-segment state, shift and loss
+            targets = batch["labels"]
+            layout = self.packed_layout(batch, targets.device)
+            if getattr(self.args, "fused", False):
+                from . import fused
+                if fused.head_loss_supported(self.rwkv.head, targets):
+                    plan = fused.HeadPlan(targets, 0, IGNORE_INDEX, layout)     # head + loss on the labelled rows only, per-segment weights
+                    x, _ = self.preparing_embedding(batch)
+                    h, _ = self.rwkv(x, hidden_only=True, layout=layout)
+                    if fused.head_loss_supported(self.rwkv.head, targets, h):
+                        return fused.head_loss(self.rwkv.head, h, plan)
+                    return self.loss_from_logits(fused.linear(self.rwkv.head, h), targets, layout)
+            logits, targets = self(batch)
+            return self.loss_from_logits(logits, targets, layout)
         if getattr(self.args, "fused", False):
             from . import fused
             from .rwkv7 import CHUNK_LEN

@@ -401,6 +401,176 @@ def RUN_CUDA_RWKV7g_state(q, w, k, v, a, b, state0, recompute_state=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Packed rows (sample packing).  Not in the reference, which pads every sample to ctx_len (src/dataset.py:125-135): several
+# samples lie end to end in one row, each a whole number of 16-token chunks, and every sample gets exactly what the op gives
+# it as a row of its own -- the state starts from zero at its first token and no dL/dS flows back across its first token.
+# ---------------------------------------------------------------------------------------------------------------
+class PackedLayout:
+    """Where the samples of a packed (B, T) batch begin.  `seg_lens`: one list per row of token counts, each a positive multiple of
+    CHUNK_LEN, summing to T.  Built once per batch and shared by every layer; the input is validated on the host and the device
+    tensors are made from host tensors (no synchronisation with the device):
+      chunk_reset (B, T/16) uint8   1 where a chunk starts a sample (the WKV7 kernels)
+      first       (B*T,)    uint8   1 at the first token of a sample (the token-shift kernels)
+      seg_id      (B, T)    int32   index of the token's segment, counted through the batch row by row
+      segments    host list of (row, first token, end token)
+    n_samples: how many of the segments are samples as far as the loss is concerned (a packer's pad-only tail segments are not);
+    default: all of them."""
+
+    def __init__(self, seg_lens, T, device="cpu", n_samples=None):
+        rows = [[int(n) for n in row] for row in seg_lens]
+        if not rows:
+            raise ValueError("PackedLayout: no rows")
+        T = int(T)
+        self.segments = []
+        reset = torch.zeros(len(rows), T // CHUNK_LEN, dtype=torch.uint8)
+        first = torch.zeros(len(rows), T, dtype=torch.uint8)
+        seg_id = torch.empty(len(rows), T, dtype=torch.int32)
+        for b, row in enumerate(rows):
+            if not row or any(n <= 0 or n % CHUNK_LEN for n in row):
+                raise ValueError(f"PackedLayout: row {b}: segment lengths must be positive multiples of {CHUNK_LEN}, got {row}")
+            if sum(row) != T:
+                raise ValueError(f"PackedLayout: row {b}: segment lengths sum to {sum(row)}, expected T = {T}")
+            t0 = 0
+            for n in row:
+                reset[b, t0 // CHUNK_LEN] = 1
+                first[b, t0] = 1
+                seg_id[b, t0:t0 + n] = len(self.segments)
+                self.segments.append((b, t0, t0 + n))
+                t0 += n
+        self.seg_lens, self.B, self.T = rows, len(rows), T
+        self.n_segments = len(self.segments)
+        self.n_samples = self.n_segments if n_samples is None else int(n_samples)
+        if not 1 <= self.n_samples <= self.n_segments:
+            raise ValueError(f"PackedLayout: n_samples = {n_samples} with {self.n_segments} segments")
+        self.device = torch.device(device)
+        self.chunk_reset = reset.to(self.device, non_blocking=True)
+        self.first = first.view(-1).to(self.device, non_blocking=True)
+        self.seg_id = seg_id.to(self.device, non_blocking=True)
+
+    def check(self, B, T, device):
+        if (self.B, self.T) != (B, T):
+            raise ValueError(f"PackedLayout: built for a ({self.B}, {self.T}) batch, used with ({B}, {T})")
+        if self.chunk_reset.device != device:
+            raise ValueError(f"PackedLayout: lives on {self.chunk_reset.device}, the tensors on {device}")
+
+
+def wkv7_forward_packed(w, q, k, v, z, a, layout, s_ckpt=None, sa=None):
+    """vrwkv_wkv7_forward_packed_bf16: y of a packed batch; with buffers s_ckpt (B,H,T/16,64,64) / sa (B,T,H,64) also the training by-products."""
+    B, T, H = _dims(w)
+    for n, t in zip("wqkvza", (w, q, k, v, z, a)):
+        _check_act(n, t, B, T, H)
+    layout.check(B, T, w.device)
+    if (s_ckpt is None) != (sa is None):
+        raise ValueError("wkv7: s_ckpt and sa go together")
+    if s_ckpt is not None:
+        _check_state(s_ckpt, sa, B, T, H, w.device)
+    y = torch.empty_like(v)
+    lib = hip_lib.load()
+    with torch.cuda.device(w.device):
+        stream = torch.cuda.current_stream(w.device).cuda_stream
+        rc = _timed("fwd_packed", B * T * H * HEAD_SIZE, w.device, lambda: lib.vrwkv_wkv7_forward_packed_bf16(
+            B, T, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(), a.data_ptr(), y.data_ptr(),
+            layout.chunk_reset.data_ptr(), s_ckpt.data_ptr() if s_ckpt is not None else 0, sa.data_ptr() if sa is not None else 0, stream))
+    hip_lib.check(rc, "vrwkv_wkv7_forward_packed_bf16")
+    return y
+
+
+_ESHAPE = -2          # VRWKV_ESHAPE
+
+
+def wkv7_backward_packed(w, q, k, v, z, a, dy, s, sa, layout):
+    """vrwkv_wkv7_backward_packed_bf16 -> (dw, dq, dk, dv, dz, da).  Where that entry has no kernel for the launch (VRWKV_ESHAPE: the backward
+    override at 5, a single row of 4 GiB and more) the plain op runs once per segment on contiguous slices; `s` and `sa` of the packed forward
+    are, segment by segment, what it wants."""
+    B, T, H = _dims(w)
+    for n, t in zip(("w", "q", "k", "v", "z", "a", "dy"), (w, q, k, v, z, a, dy)):
+        _check_act(n, t, B, T, H)
+    _check_state(s, sa, B, T, H, w.device)
+    layout.check(B, T, w.device)
+    grads = [torch.empty_like(w) for _ in range(6)]
+    lib = hip_lib.load()
+    with torch.cuda.device(w.device):
+        stream = torch.cuda.current_stream(w.device).cuda_stream
+        rc = _timed("bwd_packed", B * T * H * HEAD_SIZE, w.device, lambda: lib.vrwkv_wkv7_backward_packed_bf16(
+            B, T, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(), a.data_ptr(), dy.data_ptr(),
+            s.data_ptr(), sa.data_ptr(), layout.chunk_reset.data_ptr(), *[g.data_ptr() for g in grads], stream))
+    if rc == _ESHAPE:
+        for b, t0, t1 in layout.segments:
+            cut = [x[b:b + 1, t0:t1].contiguous() for x in (w, q, k, v, z, a, dy)]
+            part = [torch.empty_like(cut[0]) for _ in range(6)]
+            torch.ops.wind_backstepping.backward(*cut, s[b:b + 1, :, t0 // CHUNK_LEN:t1 // CHUNK_LEN].contiguous(), sa[b:b + 1, t0:t1].contiguous(), *part)
+            for g, x in zip(grads, part):
+                g[b:b + 1, t0:t1] = x
+            grads[0][b, t0] = 0                     # as the packed kernel: dL/dw of a sample's first token is exactly 0
+        return tuple(grads)
+    hip_lib.check(rc, "vrwkv_wkv7_backward_packed_bf16")
+    return tuple(grads)
+
+
+class WindBacksteppingPacked(torch.autograd.Function):
+    """WindBackstepping on a packed batch: (w, q, k, v, z, b, layout, recompute_state=False) -> y, one launch each way on device tensors
+    (vrwkv_wkv7_forward_packed_bf16 / vrwkv_wkv7_backward_packed_bf16).  Like WindBackstepping it skips the by-products when nobody asks
+    for a gradient and regenerates them in the backward under recompute_state.  The sequence-parallel training path is not used here.
+    CPU tensors do not come here: RUN_CUDA_RWKV7g_packed runs the plain op once per segment for them."""
+
+    @staticmethod
+    def forward(ctx, w, q, k, v, z, b, layout, recompute_state=False):
+        B, T, H, C = w.shape
+        assert T % CHUNK_LEN == 0
+        assert all(i.dtype == torch.bfloat16 for i in [w, q, k, v, z, b])
+        assert all(i.is_contiguous() for i in [w, q, k, v, z, b])
+        ctx.layout = layout
+        if not any(ctx.needs_input_grad[:6]):            # nobody will ask for a gradient: no by-products
+            ctx.recompute = False
+            return wkv7_forward_packed(w, q, k, v, z, b, layout)
+        ctx.recompute = bool(recompute_state)
+        if ctx.recompute:                                # y only; the backward regenerates s and sa
+            ctx.save_for_backward(w, q, k, v, z, b)
+            return wkv7_forward_packed(w, q, k, v, z, b, layout)
+        s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
+        sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+        y = wkv7_forward_packed(w, q, k, v, z, b, layout, s_ckpt=s, sa=sa)
+        ctx.save_for_backward(w, q, k, v, z, b, s, sa)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.recompute:
+            w, q, k, v, z, b = ctx.saved_tensors
+            B, T, H, C = w.shape
+            s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
+            sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+            wkv7_forward_packed(w, q, k, v, z, b, ctx.layout, s_ckpt=s, sa=sa)
+        else:
+            w, q, k, v, z, b, s, sa = ctx.saved_tensors
+        assert dy.dtype == w.dtype
+        return (*wkv7_backward_packed(w, q, k, v, z, b, dy.contiguous(), s, sa, ctx.layout), None, None)
+
+
+def RUN_CUDA_RWKV7g_packed(q, w, k, v, a, b, layout, recompute_state=False):
+    """RUN_CUDA_RWKV7g on a packed batch: (B,T,HC) views -> (B,T,H,64), the same (w,q,...) re-order.  Device tensors: one packed launch each way.
+    CPU tensors: the existing op once per segment on contiguous slices (autograd joins the pieces) -- the statement of what the packed
+    kernels compute."""
+    B, T, HC = q.shape
+    layout.check(B, T, q.device)
+    q, w, k, v, a, b = [i.view(B, T, HC // 64, 64) for i in [q, w, k, v, a, b]]
+    if _native(q):
+        return WindBacksteppingPacked.apply(w, q, k, v, a, b, layout, recompute_state).view(B, T, HC)
+    rows = []
+    for r, lens in enumerate(layout.seg_lens):
+        t0, parts = 0, []
+        for n in lens:
+            cut = [x[r:r + 1, t0:t0 + n].contiguous() for x in (w, q, k, v, a, b)]
+            # w of a sample's first token multiplies the zero state before it: its gradient is exactly 0, and is made so here as in the
+            # packed kernel (the plain op's backward leaves a cancellation residue there)
+            cut[0] = torch.cat([cut[0][:, :1].detach(), cut[0][:, 1:]], dim=1)
+            parts.append(WindBackstepping.apply(*cut))
+            t0 += n
+        rows.append(torch.cat(parts, dim=1))
+    return torch.cat(rows, dim=0).view(B, T, HC)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Stateful generation (SURVEY.md 8f rank 1).  Not in the reference, whose generate() re-runs the full forward for
 # every new token (src/model.py:513-529); same recurrence, state carried between calls.
 # ---------------------------------------------------------------------------------------------------------------
