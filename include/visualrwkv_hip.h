@@ -171,6 +171,25 @@ int vrwkv_ln_mix_bwd_packed_bf16(long ntok, int T, int C, int M, const void* xn,
 int vrwkv_mix_bwd_ln_packed_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
                                  const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second,
                                  const unsigned char* first, void* dx, float* dmu, float* ws, void* stream);
+/* The same three entries for one segment of a longer row (training across a cut in the sequence, visualrwkv_amd/visual.py::train_step_cut):
+ *   y_prev  (B, C) bf16, B = ntok / T: the LayerNorm output of the row before each sample's first row; it takes the place of the zeros at
+ *           n % T == 0.  NULL = zeros.
+ *   y_last  (B, C) bf16: receives the LayerNorm output of each sample's last row.  NULL = not wanted.
+ *   dy_last (B, C) fp32: the gradient that reaches the LayerNorm output of each sample's last row from the segment after it; it is added where
+ *           a continuing row would add its term.  NULL = none.
+ *   dy_prev (B, C) fp32: receives the gradient of y_prev.  NULL = not wanted.
+ * fp32 because the kernels form that sum in fp32 and round once: a row cut into segments gets the input gradient of the uncut row bit for bit.
+ * With every carry pointer NULL these are the entries above, bit for bit (the same kernel templates with the pointers switched off). */
+int vrwkv_ln_mix_fwd_carry_bf16(long ntok, int T, int C, float eps, int M, const void* x, const void* delta, const void* w, const void* b,
+                                const void* const* mu, void* xn, void* const* out, float* mean, float* rstd, const void* y_prev, void* y_last,
+                                void* stream);
+int vrwkv_ln_mix_bwd_carry_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* w,
+                                const void* b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* dres,
+                                const void* y_prev, const float* dy_last, float* dy_prev, void* dx, float* dwb, float* dmu, float* ws,
+                                void* stream);
+int vrwkv_mix_bwd_ln_carry_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
+                                const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* y_prev,
+                                const float* dy_last, float* dy_prev, void* dx, float* dmu, float* ws, void* stream);
 /* Inference form for the frozen ViT towers: xn = x + delta * dscale (dscale = LayerScale gamma (C) bf16 or NULL; delta NULL: no
  * add, xn not written), y = LayerNorm(xn); no statistics kept (timm blocks via src/vision.py:123-134, src/sam.py:231-247). */
 int vrwkv_add_ln_scaled_fwd_bf16(long ntok, int C, float eps, const void* x, const void* delta, const void* dscale, const void* w,

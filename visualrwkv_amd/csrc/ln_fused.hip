@@ -151,6 +151,32 @@ int vrwkv_ln_mix_fwd_packed_bf16(long ntok, int T, int C, float eps, int M, cons
     return e == hipSuccess ? VRWKV_OK : (int)e;
 }
 
+// the same for one segment of a longer row (training across a cut): y_prev (B, C) bf16 = the LayerNorm output of the row before each sample's
+// first row (NULL = zeros), y_last (B, C) bf16 receives the LayerNorm output of each sample's last row (NULL = not wanted).  Both NULL = the
+// plain entry.
+int vrwkv_ln_mix_fwd_carry_bf16(long ntok, int T, int C, float eps, int M, const void* x, const void* delta, const void* w, const void* b,
+                                const void* const* mu, void* xn, void* const* out, float* mean, float* rstd, const void* y_prev, void* y_last,
+                                void* stream) {
+    if (!y_prev && !y_last) return vrwkv_ln_mix_fwd_packed_bf16(ntok, T, C, eps, M, x, delta, w, b, mu, xn, out, mean, rstd, nullptr, stream);
+    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !x || !w || !b || !mu || !out || !mean || !rstd || (delta && !xn)) return VRWKV_EINVAL;
+    if (!ln_ok(C) || (M != 1 && M != 6)) return VRWKV_ESHAPE;
+    LmPtrs pm{}; LmOuts po{};
+    for (int j = 0; j < M; ++j) {
+        if (!mu[j] || !out[j]) return VRWKV_EINVAL;
+        pm.p[j] = (const uint16_t*)mu[j]; po.p[j] = (uint16_t*)out[j];
+    }
+    const dim3 grid(ln_grid(ntok, LN_MIX_ROWS_PER_WG)), block(ln_threads(C));
+    hipStream_t st = (hipStream_t)stream;
+    if (M == 1) hipLaunchKernelGGL((ln_mix_fwd_kernel<1, false, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
+                                   (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po, (const unsigned char*)nullptr,
+                                   (const uint16_t*)y_prev, (uint16_t*)y_last);
+    else hipLaunchKernelGGL((ln_mix_fwd_kernel<6, false, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
+                            (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po, (const unsigned char*)nullptr,
+                            (const uint16_t*)y_prev, (uint16_t*)y_last);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VRWKV_OK : (int)e;
+}
+
 // dx = dres + LN'(gradient of the lerps' input), dwb = (dgamma, dbeta) (2, C) fp32, dmu (M, C) fp32; dres may be NULL;
 // ws: vrwkv_ln_mix_ws_floats(ntok, C, M) floats.  M = 1 only: with six lerps the kernel keeps ~200 values per thread (48 gradient
 // accumulators, the prefetched rows) and hipcc spills inside the token loop at two workgroups per CU (1.02 ms against 0.72 ms for
@@ -183,6 +209,35 @@ int vrwkv_ln_mix_bwd_packed_bf16(long ntok, int T, int C, int M, const void* xn,
     if (first) LN_MIX_BWD(1, false, true); else LN_MIX_BWD(1, false, false);
 #undef LN_MIX_BWD
 #undef LN_MIX_BWD_LB
+    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, st, G, 2L * C, part_ln, dwb);
+    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)((long)M * C / 16)), dim3(256), 0, st, G, (long)M * C, part_mu, dmu);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VRWKV_OK : (int)e;
+}
+
+// the channel-mix backward for one segment of a longer row: y_prev as in the forward; dy_last (B, C) fp32 = the gradient the next segment sends
+// to the LayerNorm output of each sample's last row (NULL = none), dy_prev (B, C) fp32 receives the gradient of y_prev (NULL = not wanted).
+// All three NULL = the plain entry.
+int vrwkv_ln_mix_bwd_carry_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* w,
+                                const void* b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* dres,
+                                const void* y_prev, const float* dy_last, float* dy_prev, void* dx, float* dwb, float* dmu, float* ws,
+                                void* stream) {
+    if (!y_prev && !dy_last && !dy_prev)
+        return vrwkv_ln_mix_bwd_packed_bf16(ntok, T, C, M, xn, mean, rstd, w, b, mu, dout, dout3_second, dres, nullptr, dx, dwb, dmu, ws, stream);
+    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !xn || !mean || !rstd || !w || !b || !mu || !dout || !dx || !dwb || !dmu || !ws) return VRWKV_EINVAL;
+    if (!ln_ok(C) || M != 1 || dout3_second) return VRWKV_ESHAPE;        // M = 6: vrwkv_mix_bwd_ln_carry_bf16 + vrwkv_add_ln_bwd_bf16
+    if (!mu[0] || !dout[0]) return VRWKV_EINVAL;
+    LmPtrs pm{}, pd{};
+    pm.p[0] = (const uint16_t*)mu[0]; pd.p[0] = (const uint16_t*)dout[0];
+    const int G = ln_mix_bwd_grid(ntok);
+    const dim3 grid(G), block(ln_threads(C));
+    hipStream_t st = (hipStream_t)stream;
+    float* part_ln = ws; float* part_mu = ws + (size_t)G * 2 * C;
+#define LN_MIX_BWD_CARRY(LB) hipLaunchKernelGGL((ln_mix_bwd_kernel<1, false, LB, false, true>), grid, block, 0, st, ntok, T, C, (const uint16_t*)xn, mean, rstd, \
+        (const uint16_t*)w, (const uint16_t*)b, pm, pd, (const uint16_t*)nullptr, (const uint16_t*)dres, (uint16_t*)dx, part_ln, part_mu,                       \
+        (const unsigned char*)nullptr, (const uint16_t*)y_prev, dy_last, dy_prev)
+    if (block.x <= 256) LN_MIX_BWD_CARRY(256); else if (block.x <= 512) LN_MIX_BWD_CARRY(512); else LN_MIX_BWD_CARRY(1024);
+#undef LN_MIX_BWD_CARRY
     hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, st, G, 2L * C, part_ln, dwb);
     hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)((long)M * C / 16)), dim3(256), 0, st, G, (long)M * C, part_mu, dmu);
     hipError_t e = hipGetLastError();

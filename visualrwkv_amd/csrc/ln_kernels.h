@@ -222,12 +222,16 @@ struct LmOuts { uint16_t* p[6]; };
 
 // PK (the _packed entries: rows that hold several samples end to end): first_tok[n] != 0 marks the first token of a sample next to n % T == 0;
 // one byte per 2 C-byte row, read once per row at a wave-uniform address.  With PK off the pointer is never read.
-template <int M, bool PK = false>
+// CARRY (the _carry entries: a row cut into segments that are trained one after the other): y_prev (B, C) bf16 = the LayerNorm output of the row
+// before each sample's first row, in place of the zeros at n % T == 0; y_last (B, C) bf16 receives the LayerNorm output of each sample's last
+// row (what `prev` holds after it).  Either may be NULL; with CARRY off neither is read.
+template <int M, bool PK = false, bool CARRY = false>
 __global__ __launch_bounds__(1024) void ln_mix_fwd_kernel(long ntok, int T, int C, float eps, const uint16_t* __restrict__ x,
                                                           const uint16_t* __restrict__ delta, const uint16_t* __restrict__ w,
                                                           const uint16_t* __restrict__ b, uint16_t* __restrict__ xn,
                                                           float* __restrict__ mean, float* __restrict__ rstd, LmPtrs mu, LmOuts out,
-                                                          const unsigned char* __restrict__ first_tok = nullptr) {
+                                                          const unsigned char* __restrict__ first_tok = nullptr,
+                                                          const uint16_t* __restrict__ y_prev = nullptr, uint16_t* __restrict__ y_last = nullptr) {
     __shared__ float red[4][MAXW][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int c0 = threadIdx.x * 8;
@@ -246,6 +250,7 @@ __global__ __launch_bounds__(1024) void ln_mix_fwd_kernel(long ntok, int T, int 
 #pragma unroll
     for (int e = 0; e < 8; ++e) prev.f[e] = 0.f;
     int tpos = (int)(n0 % T);                                    // position of row n inside its sample (one division per workgroup)
+    long samp = CARRY ? n0 / T : 0;                              // CARRY: the sample of row n, counted along (no division per row)
     for (long n = n0; n < hi; ++n) {
         const uint4 cx = nx, cd = nd;
         if (n + 1 < hi && act) {
@@ -278,7 +283,11 @@ __global__ __launch_bounds__(1024) void ln_mix_fwd_kernel(long ntok, int T, int 
         for (int e = 0; e < 8; ++e) o.f[e] = fmaf((v.f[e] - mu_) * rs, wv.f[e], bv.f[e]);
         const V8 cur = unpack8(pack8(o));                        // the bf16 value the two-kernel path stores and re-reads
         if (own) {
-            const bool first = tpos == 0 || (PK && first_tok[n] != 0);
+            bool first = tpos == 0 || (PK && first_tok[n] != 0);
+            if (CARRY && tpos == 0 && y_prev) {                  // the segment before this one ended in this row's predecessor
+                prev = unpack8(act ? ldg(y_prev + samp * C + c0) : z4);
+                first = false;
+            }
             V8 xx;
 #pragma unroll
             for (int e = 0; e < 8; ++e) xx.f[e] = (first ? 0.f : prev.f[e]) - cur.f[e];
@@ -291,9 +300,10 @@ __global__ __launch_bounds__(1024) void ln_mix_fwd_kernel(long ntok, int T, int 
                 if (act) stg(out.p[j] + n * C + c0, pack8(r));
             }
             if (threadIdx.x == 0) { mean[n] = mu_; rstd[n] = rs; }
+            if (CARRY && y_last && tpos == T - 1 && act) stg(y_last + samp * C + c0, pack8(o));
         }
         prev = cur;
-        if (++tpos == T) tpos = 0;
+        if (++tpos == T) { tpos = 0; if (CARRY) ++samp; }
     }
 }
 
@@ -324,14 +334,19 @@ DEVFN void ln_row_bwd(float (*red)[MAXW][2], int slot, int wave, int lane, int n
 // gradient accumulators per thread): rows travel packed (bf16) and are unpacked where used, the previous row is carried as packed
 // xn + its two statistics and its LayerNorm output is recomputed, and the next row's loads are issued after this row's values
 // have been consumed and before the reduction -- the kernel needs ~2 us of HBM time per row and CU, the arithmetic ~0.3.
-template <int M, bool DUP3, int LB, bool PK = false>
+// CARRY (the _carry entries): y_prev as in the forward; dy_last (B, C) fp32 = the gradient that reaches the LayerNorm output of each sample's
+// last row from the segment after it, added to that row's A in place of a continuing row's Bv; dy_prev (B, C) fp32 receives Bv of each sample's first
+// row, the term that has nowhere to go without a carry.  fp32 both: aprev + Bv is formed in fp32 and rounded once.  Each may be NULL.
+template <int M, bool DUP3, int LB, bool PK = false, bool CARRY = false>
 __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long ntok, int T, int C, const uint16_t* __restrict__ xn,
                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
                                                         const uint16_t* __restrict__ w, const uint16_t* __restrict__ b, LmPtrs mu,
                                                         LmPtrs dout, const uint16_t* __restrict__ dout3b,
                                                         const uint16_t* __restrict__ dres, uint16_t* __restrict__ dx,
                                                         float* __restrict__ part_ln, float* __restrict__ part_mu,
-                                                        const unsigned char* __restrict__ first_tok = nullptr) {
+                                                        const unsigned char* __restrict__ first_tok = nullptr,
+                                                        const uint16_t* __restrict__ y_prev = nullptr, const float* __restrict__ dy_last = nullptr,
+                                                        float* __restrict__ dy_prev = nullptr) {
     __shared__ float red[2][MAXW][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int c0 = threadIdx.x * 8;
@@ -359,6 +374,13 @@ __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long 
         for (int e = 0; e < 8; ++e) o.f[e] = fmaf((xv.f[e] - m0) * r0, wv.f[e], bv.f[e]);
         return unpack8(pack8(o));
     };
+    // CARRY: 8 floats of a (B, C) fp32 carry row; inactive lanes read column 0 like every other load here
+    auto ld8 = [&](const float* p) {
+        const float4 a = *reinterpret_cast<const float4*>(p), c = *reinterpret_cast<const float4*>(p + 4);
+        V8 r;
+        r.f[0] = a.x; r.f[1] = a.y; r.f[2] = a.z; r.f[3] = a.w; r.f[4] = c.x; r.f[5] = c.y; r.f[6] = c.z; r.f[7] = c.w;
+        return r;
+    };
     if (lo < hi) {
         V8 aprev;
 #pragma unroll
@@ -378,6 +400,7 @@ __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long 
         nmu = mean[lo]; nrs = rstd[lo];
         int slot = 0;
         int tpos = (int)(lo % T);                                // position of row n inside its sample
+        long samp = CARRY ? lo / T : 0;                          // CARRY: the sample of row n, counted along (no division per row)
         for (long n = lo; n <= last; ++n) {
             const bool inside = n < hi, cont = tpos != 0 && !(PK && first_tok[n] != 0);      // PK: nothing goes from a sample's first row to the row before
             keep_packed(wp); keep_packed(bp);
@@ -389,9 +412,13 @@ __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long 
             V8 xx;
             {
                 const V8 y = ln_out(cx, mu_, rs);
-                const V8 yp = ln_out(xprev, muprev, rsprev);
+                const bool carried = CARRY && tpos == 0 && y_prev;          // the row before is the last one of the segment before
+                V8 yp;
+                if (carried) yp = unpack8(ldg(y_prev + samp * C + cc));
+                else yp = ln_out(xprev, muprev, rsprev);
+                const bool shifted = cont || carried;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) xx.f[e] = inside ? (cont ? yp.f[e] : 0.f) - y.f[e] : 0.f;
+                for (int e = 0; e < 8; ++e) xx.f[e] = inside ? (shifted ? yp.f[e] : 0.f) - y.f[e] : 0.f;
             }
             V8 dsum, bvv;
 #pragma unroll
@@ -411,6 +438,11 @@ __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long 
                     bvv.f[e] = fmaf(d.f[e], m.f[e], bvv.f[e]);
                     gm[j].f[e] = fmaf(d.f[e], xx.f[e], gm[j].f[e]);
                 }
+            }
+            if (CARRY && dy_prev && tpos == 0 && inside && act) {   // Bv of a sample's first row: the gradient of y_prev
+                float* dp = dy_prev + samp * C + c0;
+                *reinterpret_cast<float4*>(dp) = make_float4(bvv.f[0], bvv.f[1], bvv.f[2], bvv.f[3]);
+                *reinterpret_cast<float4*>(dp + 4) = make_float4(bvv.f[4], bvv.f[5], bvv.f[6], bvv.f[7]);
             }
             if (n + 1 <= last) {                                 // next row's loads: this row's registers are free, the reduction is ahead
                 const long o = (n + 1) * C + cc;
@@ -437,9 +469,14 @@ __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long 
             if (inside) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) aprev.f[e] = dsum.f[e] - bvv.f[e];
+                if (CARRY && dy_last && tpos == T - 1) {         // the row ends its sample: what the next segment's first row sends it takes the
+                    const V8 dl = ld8(dy_last + samp * C + cc);         // place of a continuing row's Bv -- A + Bv, formed here, + 0 where that row would add
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) aprev.f[e] += dl.f[e];
+                }
                 xprev = cx; resprev = cr; muprev = mu_; rsprev = rs;
             }
-            if (++tpos == T) tpos = 0;
+            if (++tpos == T) { tpos = 0; if (CARRY) ++samp; }
         }
         if (last == hi - 1) {                                    // no successor row: the gradient of the last row is A
             V8 xh;

@@ -188,11 +188,16 @@ DEVFN void st4f(uint16_t* p, const V4& v) {
 // recomputed here from xn and the row statistics exactly as that kernel rounded it: bf16(fma((xn - mean) rstd, gamma, beta)).
 struct LnX { const float* mean; const float* rstd; const uint16_t* w; const uint16_t* b; };
 // PK (vrwkv_mix_bwd_ln_packed_bf16: rows that hold several samples end to end): first_tok[n] != 0 marks a sample's first token next to n % T == 0.
-template <int M, bool DUP3, bool DD = false, bool LNX = false, bool PK = false>
+// CARRY (vrwkv_mix_bwd_ln_carry_bf16: one segment of a longer row): y_prev (B, C) bf16 = x of the row before each sample's first row, in place
+// of the zeros at n % T == 0; dy_last (B, C) fp32 = what the next segment sends to dx of each sample's last row, added where a continuing row
+// would add its Bv (added to that row's A as soon as it is formed); dy_prev (B, C) fp32 receives Bv of each sample's first row.  Each may be NULL; with CARRY off none is read.
+template <int M, bool DUP3, bool DD = false, bool LNX = false, bool PK = false, bool CARRY = false>
 __global__ __launch_bounds__(512) void mix_bwd_kernel(long ntok, int T, int C, const uint16_t* __restrict__ x, Ptrs6 mu, Ptrs6 dout,
                                                       const uint16_t* __restrict__ dout3b, uint16_t* __restrict__ dx,
                                                       float* __restrict__ dmu, Ptrs6 mm = Ptrs6{}, MPtrs6 dmm = MPtrs6{}, LnX ln = LnX{},
-                                                      const unsigned char* __restrict__ first_tok = nullptr) {
+                                                      const unsigned char* __restrict__ first_tok = nullptr,
+                                                      const uint16_t* __restrict__ y_prev = nullptr, const float* __restrict__ dy_last = nullptr,
+                                                      float* __restrict__ dy_prev = nullptr) {
     const long lo = ntok * blockIdx.x / gridDim.x, hi = ntok * (blockIdx.x + 1) / gridDim.x;
     for (int c0 = threadIdx.x * 4; c0 < C; c0 += blockDim.x * 4) {
         uint2 lnw = make_uint2(0u, 0u), lnb = lnw;
@@ -253,6 +258,7 @@ __global__ __launch_bounds__(512) void mix_bwd_kernel(long ntok, int T, int C, c
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { dsum.f[e] += d[j].f[e]; bv.f[e] = fmaf(d[j].f[e], w.f[e], bv.f[e]); }
             }
+            const bool opens = CARRY && n % T == 0;                  // row n opens a sample (and a segment of a cut row)
             if (n > lo) {
                 V4 o;
 #pragma unroll
@@ -260,15 +266,27 @@ __global__ __launch_bounds__(512) void mix_bwd_kernel(long ntok, int T, int C, c
                 st4f(dx + (n - 1) * C + c0, o);
             }
             if (inside) {
+                bool shifted = cont;
+                if (opens && y_prev) {
+                    const V4 t = ld4f(y_prev + (n / T) * C + c0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) xprev.f[e] = t.f[e];
+                    shifted = true;
+                }
+                if (opens && dy_prev) *reinterpret_cast<float4*>(dy_prev + (n / T) * C + c0) = make_float4(bv.f[0], bv.f[1], bv.f[2], bv.f[3]);
                 V4 xxv;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float xx = (cont ? xprev.f[e] : 0.f) - xv.f[e];
+                    const float xx = (shifted ? xprev.f[e] : 0.f) - xv.f[e];
                     xxv.f[e] = xx;
 #pragma unroll
                     for (int j = 0; j < M; ++j) gm[j].f[e] = fmaf(d[j].f[e], xx, gm[j].f[e]);
                     aprev.f[e] = dsum.f[e] - bv.f[e];
                     xprev.f[e] = xv.f[e];
+                }
+                if (CARRY && dy_last && n % T == T - 1) {            // the row closes its sample: the next segment's Bv in place of a continuing row's
+                    const float4 t = *reinterpret_cast<const float4*>(dy_last + (n / T) * C + c0);
+                    aprev.f[0] += t.x; aprev.f[1] += t.y; aprev.f[2] += t.z; aprev.f[3] += t.w;
                 }
                 if (DD) {
 #pragma unroll
@@ -762,6 +780,31 @@ int vrwkv_mix_bwd_ln_packed_bf16(long ntok, int T, int C, int M, const void* xn,
     else if (first) hipLaunchKernelGGL((mix_bwd_kernel<6, false, false, true, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln, first);
     else if (d2) hipLaunchKernelGGL((mix_bwd_kernel<6, true, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln);
     else hipLaunchKernelGGL((mix_bwd_kernel<6, false, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln);
+    colsum(G, (long)M * C, ws, dmu, st);
+    return done();
+}
+
+// the same for one segment of a longer row (training across a cut): y_prev (B, C) bf16 = the LayerNorm output of the row before each sample's
+// first row (NULL = zeros); dy_last (B, C) fp32 = the gradient the next segment sends to the LayerNorm output of each sample's last row (NULL =
+// none); dy_prev (B, C) fp32 receives the gradient of y_prev (NULL = not wanted).  All three NULL = vrwkv_mix_bwd_ln_bf16.
+int vrwkv_mix_bwd_ln_carry_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
+                                const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* y_prev,
+                                const float* dy_last, float* dy_prev, void* dx, float* dmu, float* ws, void* stream) {
+    if (!y_prev && !dy_last && !dy_prev)
+        return vrwkv_mix_bwd_ln_packed_bf16(ntok, T, C, M, xn, mean, rstd, ln_w, ln_b, mu, dout, dout3_second, nullptr, dx, dmu, ws, stream);
+    if (ntok <= 0 || T <= 0 || !xn || !mean || !rstd || !ln_w || !ln_b || !mu || !dout || !dx || !dmu || !ws || M != 6) return VRWKV_EINVAL;
+    if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
+    Ptrs6 m{}, d{};
+    for (int i = 0; i < M; ++i) { m.p[i] = (const uint16_t*)mu[i]; d.p[i] = (const uint16_t*)dout[i]; if (!m.p[i] || !d.p[i]) return VRWKV_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    const int G = bwd_grid(ntok);
+    const int threads = C / 4 < 512 ? C / 4 : 512;
+    const uint16_t* d2 = (const uint16_t*)dout3_second;
+    const LnX ln{mean, rstd, (const uint16_t*)ln_w, (const uint16_t*)ln_b};
+    if (d2) hipLaunchKernelGGL((mix_bwd_kernel<6, true, false, true, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws,
+                               Ptrs6{}, MPtrs6{}, ln, (const unsigned char*)nullptr, (const uint16_t*)y_prev, dy_last, dy_prev);
+    else hipLaunchKernelGGL((mix_bwd_kernel<6, false, false, true, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws,
+                            Ptrs6{}, MPtrs6{}, ln, (const unsigned char*)nullptr, (const uint16_t*)y_prev, dy_last, dy_prev);
     colsum(G, (long)M * C, ws, dmu, st);
     return done();
 }

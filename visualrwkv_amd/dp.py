@@ -21,7 +21,9 @@ reduce-scatter is emulated with all-reduce + slice and the optimizer uses a torc
 """
 from __future__ import annotations
 
+import contextlib
 import math
+import weakref
 from typing import List, Optional
 
 import torch
@@ -120,6 +122,7 @@ class Zero1Engine:
                 # where this parameter's gradient lives: a backward that owns its weight-gradient GEMM (fused._LinearTN) writes it
                 # there directly and returns that view, which the hook below recognises by its address -- no copy into the bucket
                 p._vrwkv_flat_grad = (self.flat_grad, o)
+                p._vrwkv_engine = weakref.ref(self)      # VisualRWKV.train_step_cut finds hold_reductions() through its parameters
         # buckets
         self.buckets: List[_Bucket] = []
         s = 0
@@ -158,6 +161,7 @@ class Zero1Engine:
         for k, p in enumerate(ordered):
             self._hooks.append(p.register_post_accumulate_grad_hook(self._make_hook(k)))
         self._sq = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._hold = False
         self._gather = False
         self._next_launch = 0
         self._gather_event = None
@@ -199,6 +203,14 @@ class Zero1Engine:
             g = param.grad
             o = self.offsets[k]
             param._vrwkv_wgrad_pending = False          # see fused._LinearTN.backward
+            if self._hold:                              # hold_reductions(): several backward calls per step -- count a parameter once, launch nothing
+                if g.data_ptr() != self.flat_grad.data_ptr() + o * self.flat_grad.element_size():
+                    self._stash[k] = g                  # the second and later calls add into this same tensor (autograd accumulates in place)
+                if not self._fired[k]:
+                    self._fired[k] = True
+                    for i in self._param_buckets[k]:
+                        self.buckets[i].pending -= 1
+                return
             if g.data_ptr() != self.flat_grad.data_ptr() + o * self.flat_grad.element_size():
                 self._stash[k] = g                   # autograd handed over a fresh tensor: copied bucket-wise
             self._fired[k] = True
@@ -206,6 +218,22 @@ class Zero1Engine:
                 self.buckets[i].pending -= 1
             self._launch_ready()
         return hook
+
+    @contextlib.contextmanager
+    def hold_reductions(self):
+        """Several backward calls in one step (VisualRWKV.train_step_cut: one per segment of a cut row).  The hooks assume that a
+        parameter's gradient is final when its hook has fired once; inside this context they only accumulate -- `.grad` keeps growing in
+        place, in the stashed tensor or in the flat buffer -- and nothing is reduced.  On exit the complete buckets are flushed and reduced
+        in index order, each exactly once; buckets with parameters that never fired wait for step(), as ever."""
+        if self._hold:                                  # nested: the outermost context releases
+            yield self
+            return
+        self._hold = True
+        try:
+            yield self
+        finally:
+            self._hold = False
+        self._launch_ready()
 
     def _launch_ready(self):
         """Reduce complete buckets strictly in index order: every rank issues the same sequence of collectives, whatever
@@ -410,7 +438,7 @@ class Zero1Engine:
         self._hooks, self._wait_hooks = [], []
         self._stash = [None] * len(self._stash)
         for p in self.params:
-            for attr in ("_vrwkv_flat_grad", "_vrwkv_flat_armed", "_vrwkv_wgrad_pending"):
+            for attr in ("_vrwkv_flat_grad", "_vrwkv_flat_armed", "_vrwkv_wgrad_pending", "_vrwkv_engine"):
                 if hasattr(p, attr):
                     delattr(p, attr)
 

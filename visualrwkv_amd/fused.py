@@ -694,8 +694,97 @@ class _AddLnMix(torch.autograd.Function):
         return (dx, (dx if ctx.has_delta else None), dwb[0], dwb[1], None, None, None, *[dmu[i].view(sh) for i, sh in enumerate(ctx.mu_shapes)])
 
 
-def add_ln_mix(x, delta, ln, mus, dup3=False, first=None):
-    """Returns (x + delta, [lerp outputs]) -- see `_AddLnMix`.  first: the marks of a wkv7.PackedLayout (layout.first) for packed rows."""
+class _AddLnMixCarry(torch.autograd.Function):
+    """`_AddLnMix` for one segment of a longer row (training across a cut; the _carry entries of csrc/ln_fused.hip / tmix_fused.hip):
+    (xn, out_0 .. out_{M-1}[, alias of out_3], y_last) from (x, delta, y_prev).  y_prev (B, C), or None = zeros: the LayerNorm output of the
+    token before the segment, which the shift reads at t = 0; it may require a gradient.  y_last (B, C): the LayerNorm output of the
+    segment's last token, a differentiable output.  y_last is returned in fp32 (it holds bf16 values): its gradient -- the next segment's
+    gradient of y_prev -- then stays fp32 between the two kernels, which add it in fp32 and round once, as they do inside a row."""
+
+    @staticmethod
+    def forward(ctx, x, delta, w, b, eps, dup3, y_prev, *mus):
+        B, T, C = x.shape
+        M = len(mus)
+        x = x.contiguous()
+        delta = delta.contiguous() if delta is not None else None
+        wc, bc = w.contiguous(), b.contiguous()
+        mus_c = [m.reshape(C).contiguous() for m in mus]
+        yp = None
+        if y_prev is not None:
+            if tuple(y_prev.shape) != (B, C) or y_prev.device != x.device:
+                raise ValueError(f"add_ln_mix: y_prev must be ({B}, {C}) on {x.device}, got {tuple(y_prev.shape)} on {y_prev.device}")
+            yp = y_prev.detach().to(torch.bfloat16).contiguous()
+        _chk(x, delta, wc, bc, yp, *mus_c)
+        ntok = B * T
+        xn = torch.empty_like(x) if delta is not None else x
+        outs = [torch.empty_like(x) for _ in mus]
+        mean = torch.empty(ntok, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(ntok, dtype=torch.float32, device=x.device)
+        y_last = torch.empty(B, C, dtype=torch.bfloat16, device=x.device)
+        rc = hip_lib.load().vrwkv_ln_mix_fwd_carry_bf16(ntok, T, C, float(eps), M, x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
+                                                        _ptr_array(mus_c), xn.data_ptr() if delta is not None else 0, _ptr_array(outs),
+                                                        mean.data_ptr(), rstd.data_ptr(), _p(yp), y_last.data_ptr(), _stream(x))
+        hip_lib.check(rc, "vrwkv_ln_mix_fwd_carry_bf16")
+        ctx.save_for_backward(xn, mean, rstd, wc, bc, *mus_c, *([yp] if yp is not None else []))
+        ctx.has_prev = yp is not None
+        ctx.prev_dtype = y_prev.dtype if y_prev is not None else None
+        ctx.has_delta = delta is not None
+        ctx.mu_shapes = [m.shape for m in mus]
+        ctx.M = M
+        if dup3:
+            outs.append(outs[3].view_as(outs[3]))
+        return (xn, *outs, y_last.float())
+
+    @staticmethod
+    def backward(ctx, d_xn, *grads):
+        M = ctx.M
+        xn, mean, rstd, wc, bc, *rest = ctx.saved_tensors
+        mus_c, yp = rest[:M], (rest[M] if ctx.has_prev else None)
+        *douts, dy_last = grads
+        B, T, C = xn.shape
+        douts = [d.contiguous() for d in douts]
+        d_xn = d_xn.contiguous() if d_xn is not None else None
+        _chk(d_xn, *douts)
+        dy_last = dy_last.float().contiguous()
+        second = douts[M] if len(douts) > M else None
+        ntok = B * T
+        dx = torch.empty_like(xn)
+        dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
+        dmu = torch.empty(M, C, dtype=torch.float32, device=xn.device)
+        dy_prev = torch.empty(B, C, dtype=torch.float32, device=xn.device) if (yp is not None and ctx.needs_input_grad[6]) else None
+        lib = hip_lib.load()
+        if M == 1:
+            ws = torch.empty(lib.vrwkv_ln_mix_ws_floats(ntok, C, M), dtype=torch.float32, device=xn.device)
+            rc = lib.vrwkv_ln_mix_bwd_carry_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
+                                                 _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), _p(d_xn), _p(yp), dy_last.data_ptr(),
+                                                 _p(dy_prev), dx.data_ptr(), dwb.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
+            hip_lib.check(rc, "vrwkv_ln_mix_bwd_carry_bf16")
+        else:       # six lerps: their backward with the LayerNorm output recomputed in place of a stored one, then the LayerNorm's
+            dy = torch.empty_like(xn)
+            ws = _ws(ntok, C, M, xn.device)
+            rc = lib.vrwkv_mix_bwd_ln_carry_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
+                                                 _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), _p(yp), dy_last.data_ptr(), _p(dy_prev),
+                                                 dy.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
+            hip_lib.check(rc, "vrwkv_mix_bwd_ln_carry_bf16")
+            ws = torch.empty(lib.vrwkv_add_ln_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
+            rc = lib.vrwkv_add_ln_bwd_bf16(ntok, C, dy.data_ptr(), _p(d_xn), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                           wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
+            hip_lib.check(rc, "vrwkv_add_ln_bwd_bf16")
+        dwb = dwb.to(wc.dtype)
+        dmu = dmu.to(xn.dtype)
+        return (dx, (dx if ctx.has_delta else None), dwb[0], dwb[1], None, None, dy_prev.to(ctx.prev_dtype) if dy_prev is not None else None,
+                *[dmu[i].view(sh) for i, sh in enumerate(ctx.mu_shapes)])
+
+
+def add_ln_mix(x, delta, ln, mus, dup3=False, first=None, carry=None):
+    """Returns (x + delta, [lerp outputs]) -- see `_AddLnMix`.  first: the marks of a wkv7.PackedLayout (layout.first) for packed rows.
+    carry: a 1-tuple (y_prev,) when x is one segment of a longer row (y_prev may be None: the row starts here); returns
+    (x + delta, [lerp outputs], y_last) then -- see `_AddLnMixCarry`."""
+    if carry is not None:
+        if first is not None:
+            raise NotImplementedError("add_ln_mix: a carry together with packed rows")
+        xn, *outs, y_last = _AddLnMixCarry.apply(x, delta, ln.weight, ln.bias, ln.eps, dup3, carry[0], *mus)
+        return xn, outs, y_last
     xn, *outs = _AddLnMix.apply(x, delta, ln.weight, ln.bias, ln.eps, dup3, first, *mus)
     return xn, outs
 
@@ -703,6 +792,12 @@ def add_ln_mix(x, delta, ln, mus, dup3=False, first=None):
 def packed_supported(x):
     """May a packed batch (wkv7.PackedLayout) take blocks_forward?  It needs both shifts inside the ln_mix kernels: the two-kernel shift
     (VRWKV_LN_MIX=0 / VRWKV_LN_MIX_TMIX=0, vrwkv_mix_fwd / _bwd) finds a first token as n % T == 0 only; the caller runs the unfused Blocks then."""
+    return ln_mix_supported(x) and LN_MIX_TMIX
+
+
+def carry_supported(x):
+    """May one segment of a cut row (rwkv7.TrainCarry) take blocks_forward?  As for packed rows, both shifts must be inside the ln_mix kernels;
+    the caller runs the unfused Blocks otherwise."""
     return ln_mix_supported(x) and LN_MIX_TMIX
 
 
@@ -718,12 +813,24 @@ def add_ln_supported(x):
     return x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 64 == 0 and x.shape[-1] <= 8192
 
 
-def _block_segment(block, x, delta, v_first, selective=False, layout=None):
+def _block_segment(block, x, delta, v_first, selective=False, layout=None, carry=None):
     """One Block on the (x, pending delta) residual stream: returns (x + delta, ffn output still to be added, v_first).
     selective: the selective-recompute mode of blocks_forward (WKV7 by-products and relu(h)^2 are re-formed in the backward).
-    layout: a wkv7.PackedLayout -- both token shifts and the WKV7 state restart at every sample of a row (packed_supported(x) must hold)."""
+    layout: a wkv7.PackedLayout -- both token shifts and the WKV7 state restart at every sample of a row (packed_supported(x) must hold).
+    carry: this layer's (att_x, ffn_x, S) of a rwkv7.TrainCarry (x is one segment of a longer row; carry_supported(x) must hold): the result
+    gains the layer's next carry (att_x, ffn_x, S) as three more entries."""
     att, ffn = block.att, block.ffn
     fuse = ln_mix_supported(x) and getattr(att.args, "fused", False)
+    if carry is not None:
+        if layout is not None:
+            raise NotImplementedError("a training carry together with packed rows")
+        if not (fuse and LN_MIX_TMIX):
+            raise NotImplementedError("a cut row needs the fused ln_mix kernels for both token shifts (fused.carry_supported)")
+        dup3 = torch.is_grad_enabled() and GRAD_ALIAS and att.layer_id > 0
+        x, mixed, att_x = add_ln_mix(x, delta, block.ln1, (att.x_r, att.x_w, att.x_k, att.x_v, att.x_a, att.x_g), dup3, None, (carry[0],))
+        att_out, v_first, s_end = tmix_from_mixed(att, mixed, v_first, recompute_state=selective, state0=carry[2], want_state=True)
+        x, (k,), ffn_x = add_ln_mix(x, att_out, block.ln2, (ffn.x_k,), False, None, (carry[1],))
+        return x, cmix_from_mixed(ffn, k, recompute_relusq=selective), v_first, att_x, ffn_x, s_end
     first = layout.first if layout is not None else None
     if layout is not None and not (fuse and LN_MIX_TMIX):
         raise NotImplementedError("packed rows need the fused ln_mix kernels for both token shifts (fused.packed_supported)")
@@ -741,7 +848,12 @@ def _block_segment(block, x, delta, v_first, selective=False, layout=None):
     return x, ffn(h), v_first
 
 
-def blocks_forward(rwkv, x, grad_cp=0, layout=None):
+def _block_segment_carry(block, x, delta, v_first, selective, att_x, ffn_x, S):
+    """_block_segment with the carry tensors as arguments of their own: what blocks_forward's mode 1 checkpoints."""
+    return _block_segment(block, x, delta, v_first, selective, None, (att_x, ffn_x, S))
+
+
+def blocks_forward(rwkv, x, grad_cp=0, layout=None, carry=None):
     """All Blocks + ln_out with the residual adds fused into the LayerNorms (same math as Block.forward chained,
     src/model.py:247-254,313-318): the residual stream is carried as (x, pending delta).
     grad_cp (the reference's memory-saving switch, src/model.py:318-319: deepspeed.checkpointing.checkpoint per block):
@@ -753,20 +865,36 @@ def blocks_forward(rwkv, x, grad_cp=0, layout=None):
          and relu(h)^2 of the channel-mix (4 of them: one streaming kernel) -- about a third of the activation memory for ~1 ms per layer.
     (Rounds 4-5 had 1 and 2 the other way round; a trainer configured for the reference's `--grad_cp 1` must not get the mode that needs 3x
     the memory.)
-    layout: a wkv7.PackedLayout when the rows hold several samples end to end; every mode passes it to every Block."""
+    layout: a wkv7.PackedLayout when the rows hold several samples end to end; every mode passes it to every Block.
+    carry: a rwkv7.TrainCarry when x is one segment of a longer row; every mode threads it through every Block (mode 1 checkpoints the Block
+    with the carry tensors among its arguments, mode 2 lets the WKV7 state op regenerate its by-products from the carried state) and the
+    result is (hidden, the carry leaving the segment)."""
     grad_cp = int(grad_cp) if torch.is_grad_enabled() else 0
     if grad_cp not in (0, 1, 2):
         raise ValueError(f"grad_cp = {grad_cp}: 0 (keep everything), 1 (re-compute every block, the reference's recipe) or 2 (selective recompute)")
+    if carry is not None and layout is not None:
+        raise NotImplementedError("a training carry together with packed rows")
     x = rwkv.blocks[0].ln0(x)
     v_first = torch.empty_like(x)
     delta = None
-    for block in rwkv.blocks:
-        if grad_cp == 1:
+    layers = []
+    for i, block in enumerate(rwkv.blocks):
+        if carry is not None:
+            if grad_cp == 1:
+                from torch.utils.checkpoint import checkpoint
+                x, delta, v_first, *lc = checkpoint(_block_segment_carry, block, x, delta, v_first, False, *carry[i], use_reentrant=False)
+            else:
+                x, delta, v_first, *lc = _block_segment(block, x, delta, v_first, grad_cp == 2, None, carry[i])
+            layers.append(tuple(lc))
+        elif grad_cp == 1:
             from torch.utils.checkpoint import checkpoint
             x, delta, v_first = checkpoint(_block_segment, block, x, delta, v_first, False, layout, use_reentrant=False)
         else:
             x, delta, v_first = _block_segment(block, x, delta, v_first, grad_cp == 2, layout)
     _, h = add_ln(x, delta, rwkv.ln_out)
+    if carry is not None:
+        from .rwkv7 import TrainCarry
+        return h, TrainCarry(len(layers), layers)
     return h
 
 
@@ -833,9 +961,13 @@ class HeadPlan:
     long landed, so reading it waits for nothing (no device-wide synchronisation in the step).  Rows are those of the hidden state left-padded
     by `pad` rows per sample (RWKV.forward_features): pad rows carry no label and get no gradient.  Nothing is cached across batches.
     layout (a wkv7.PackedLayout; pad is 0 then): "sample" means segment of a packed row -- the last row of a segment has no target, and a
-    labelled row weighs 1 / (valid labels of its segment * layout.n_samples)."""
+    labelled row weighs 1 / (valid labels of its segment * layout.n_samples).
+    window = (a, b) (train_step_cut; pad is 0, no layout): the plan describes rows a .. b-1 of the (B, T) row `targets` -- the hidden state it
+    goes with is (B, b-a, C).  Labels and weights are the whole row's: row b-1 predicts token b of the row, a labelled row weighs
+    1 / (valid labels of its whole sample * B), and `l2_rows` (L2Wrap's B * T) counts the whole row, so that the windows' losses add up to
+    the loss of the uncut row."""
 
-    def __init__(self, targets, pad, ignore_index=-100, layout=None):
+    def __init__(self, targets, pad, ignore_index=-100, layout=None, window=None):
         B, T = targets.shape
         dev = targets.device
         labels = torch.full((B, T), ignore_index, dtype=torch.long, device=dev)
@@ -853,6 +985,14 @@ class HeadPlan:
             seg = layout.seg_id.view(-1).long()
             valid = torch.zeros(layout.n_segments, dtype=torch.float32, device=dev).index_add_(0, seg, lab).clamp_(min=1)
             self.w = lab / (valid[seg] * layout.n_samples)
+        self.l2_rows = B * T
+        if window is not None:
+            a, b_ = window
+            if layout is not None or pad != 0 or not (0 <= a < b_ <= T):
+                raise ValueError(f"HeadPlan: a window needs pad 0, no layout and 0 <= a < b <= T (got {window}, pad {pad})")
+            labels = labels[:, a:b_].contiguous()
+            self.w = self.w.view(B, T)[:, a:b_].reshape(-1)
+            T = b_ - a
         self.B, self.T, self.pad = B, T, pad
         Tp = T + pad
         lab_p = torch.full((B, Tp), -100, dtype=torch.long, device=dev)
@@ -937,7 +1077,7 @@ class _HeadCE(torch.autograd.Function):
         row_w = torch.zeros(B, Tp, dtype=torch.float32, device=dev)
         row_w[:, plan.pad:] = (plan.w * g.float()).view(B, plan.T)      # _FusedCE's row_w on the real rows, 0 on the pad rows
         row_w = row_w.view(N)
-        l2f = 1e-4 / n_real
+        l2f = 1e-4 / plan.l2_rows                                        # = n_real, except for a window of a longer row
         x2 = x.view(N, C)
         n_lab = plan.n_labelled()
         compact = n_lab <= HEAD_COMPACT_MAX_FRACTION * n_real
@@ -1131,9 +1271,11 @@ def tmix_forward(m, x, v_first, recompute_state=False, layout=None):
     return tmix_from_mixed(m, mixed, v_first, recompute_state)
 
 
-def tmix_from_mixed(m, mixed, v_first, recompute_state=False, layout=None):
+def tmix_from_mixed(m, mixed, v_first, recompute_state=False, layout=None, state0=None, want_state=False):
     """The time-mix after its token shift: `mixed` = (xr, xw, xk, xv, xa, xg[, alias of xv for its second consumer]).
-    layout: a wkv7.PackedLayout -- the WKV7 op restarts its state at every sample of a row (one packed launch each way)."""
+    layout: a wkv7.PackedLayout -- the WKV7 op restarts its state at every sample of a row (one packed launch each way).
+    want_state (one segment of a cut row): the recurrence runs through the state op from state0 (B,H,64,64) fp32 -- None: the layer's tuned
+    state, else zeros -- and the state after the last token is returned as a third result; gradients flow through both."""
     xr, xw, xk, xv, xa, xg = mixed[:6]
     xv_b = mixed[6] if len(mixed) > 6 else xv
     mm = lora_mm if torch.is_grad_enabled() and LORA_WGRAD else torch.matmul     # training: skinny weight-gradient kernel in the backward
@@ -1154,7 +1296,16 @@ def tmix_from_mixed(m, mixed, v_first, recompute_state=False, layout=None):
             k2, v2, z, b, k2_b, v2_b = kva(k, v, v_first, vl, al, m.k_k, m.k_a, m.a0, m.v0, True)
         if not GRAD_ALIAS:
             k2_b, v2_b = k2, v2
-    if layout is not None:
+    s_end = None
+    if want_state:
+        if layout is not None:
+            raise NotImplementedError("a carried state together with packed rows")
+        if state0 is None:
+            state0 = m.wkv_initial_state()
+        if state0 is None:
+            state0 = torch.zeros(r.shape[0], r.shape[2] // 64, 64, 64, dtype=torch.float32, device=r.device)
+        y, s_end = RUN_CUDA_RWKV7g_state(r, w, k2, v2, z, b, state0, recompute_state=recompute_state)
+    elif layout is not None:
         if getattr(m, "time_state", None) is not None:
             raise NotImplementedError("packed rows together with a tuned state: every segment would have to start from it")
         y = RUN_CUDA_RWKV7g_packed(r, w, k2, v2, z, b, layout, recompute_state=recompute_state)
@@ -1163,6 +1314,8 @@ def tmix_from_mixed(m, mixed, v_first, recompute_state=False, layout=None):
     else:
         y = RUN_CUDA_RWKV7g(r, w, k2, v2, z, b, recompute_state=recompute_state)
     y = post(y, r, k2_b, v2_b, g, m.ln_x.weight, m.ln_x.bias, m.r_k, m.ln_x.eps)
+    if want_state:
+        return linear(m.output, y), v_first, s_end
     return linear(m.output, y), v_first
 
 

@@ -35,13 +35,55 @@ def _ortho(rows: int, cols: int, scale: float) -> torch.Tensor:
     return w
 
 
-def time_shift(x: torch.Tensor, layout=None) -> torch.Tensor:
+def time_shift(x: torch.Tensor, layout=None, prev=None) -> torch.Tensor:
     """x_{t-1} with zeros at t = 0 of every sample (nn.ZeroPad2d((0,0,1,-1)), src/model.py:149).  With a wkv7.PackedLayout the first token
-    of every segment of a packed row reads zeros too, and no gradient goes from it to the token before."""
+    of every segment of a packed row reads zeros too, and no gradient goes from it to the token before.  prev (B, C): the token before the
+    first one (a row cut into segments, TrainCarry) in place of the zeros; gradients flow into it."""
+    if prev is not None:
+        if layout is not None:
+            raise NotImplementedError("time_shift: a carried token together with packed rows")
+        return torch.cat((prev.to(x.dtype).unsqueeze(1), x[:, :-1]), dim=1)
     xs = F.pad(x, (0, 0, 1, -1))
     if layout is not None:
         xs = xs.masked_fill(layout.first.view(x.shape[0], x.shape[1], 1).bool(), 0)
     return xs
+
+
+class TrainCarry:
+    """What crosses a cut when a long row is trained in segments (VisualRWKV.train_step_cut; not in the reference, whose training op has no
+    state).  Per layer: `att_x` / `ffn_x` (B, C) = the ln1 / ln2 output of the last token before the cut, which the time-mix / channel-mix
+    shift of the next segment reads, and `S` (B, H, 64, 64) fp32 (fp64 for an fp64 model) = the WKV state.  Unlike the inference RWKV7State
+    these are ordinary autograd tensors: the modules RETURN the next carry instead of updating one in place, and gradients flow through
+    all three.  An entry of None is the start of a row: the shift reads zeros and the state starts from zeros, or from the layer's
+    `time_state` under args.state_tune."""
+
+    def __init__(self, n_layer, layers=None):
+        self.layers = list(layers) if layers is not None else [(None, None, None)] * n_layer
+        if len(self.layers) != n_layer:
+            raise ValueError(f"TrainCarry: {len(self.layers)} layers given for a model of {n_layer}")
+
+    def __getitem__(self, i):
+        return self.layers[i]
+
+    def tensors(self):
+        """Every tensor of the carry, layer by layer (att_x, ffn_x, S); None entries are left out."""
+        return [t for layer in self.layers for t in layer if t is not None]
+
+    def detach(self, requires_grad=False):
+        """The same values cut from their graph (as leaves that collect a gradient with requires_grad)."""
+        leaf = lambda t: None if t is None else t.detach().requires_grad_(requires_grad)
+        return TrainCarry(len(self.layers), [tuple(leaf(t) for t in layer) for layer in self.layers])
+
+
+def _carry_state0(m, carry_S, B, like):
+    """The state a segment's WKV recurrence starts from: the carried one, else the layer's tuned state, else zeros."""
+    if carry_S is not None:
+        return carry_S
+    s0 = m.wkv_initial_state()
+    if s0 is not None:
+        return s0
+    return torch.zeros(B, m.n_head, m.head_size, m.head_size, device=like.device,
+                       dtype=torch.float64 if like.dtype == torch.float64 else torch.float32)
 
 
 class RWKV_Tmix_x070(nn.Module):
@@ -115,20 +157,28 @@ class RWKV_Tmix_x070(nn.Module):
             return None
         return ts if ts.dtype == torch.float64 else ts.float()
 
-    def forward(self, x, v_first, state=None, layout=None):
+    def forward(self, x, v_first, state=None, layout=None, carry=None):
         """`state` (an RWKV7State; inference: no gradient flows through it) carries the previous token and the WKV state across calls.
-        `layout` (a wkv7.PackedLayout; training on packed rows): the shift and the WKV state restart at every segment."""
+        `layout` (a wkv7.PackedLayout; training on packed rows): the shift and the WKV state restart at every segment.
+        `carry` (training across a cut, TrainCarry): (att_x, S) entering this segment, either may be None; the call then returns
+        (out, v_first, (att_x, S) leaving it), with gradients through both.  This is the PyTorch statement of the shift; the fused kernels
+        take a carry through fused.blocks_forward."""
         B, T, C = x.size()
         H = self.n_head
+        if carry is not None and (state is not None or layout is not None):
+            raise NotImplementedError("a training carry together with an inference state or packed rows")
         if layout is not None and (state is not None or getattr(self, "time_state", None) is not None):
             raise NotImplementedError("packed rows together with a carried or tuned state: every segment would have to start from it")
-        if getattr(self.args, "fused", False) and x.is_cuda and layout is None:
+        if getattr(self.args, "fused", False) and x.is_cuda and layout is None and carry is None:
             from . import fused
             if state is None:
                 return fused.tmix_forward(self, x, v_first)
             if not torch.is_grad_enabled() and x.dtype == torch.bfloat16:
                 return fused.tmix_forward_stateful(self, x, v_first, state)
-        if state is None:
+        x_last = x[:, -1]
+        if carry is not None:
+            xx = time_shift(x, None, carry[0]) - x
+        elif state is None:
             xx = time_shift(x, layout) - x
         else:
             xx = torch.cat((state.att_x[self.layer_id].unsqueeze(1), x[:, :-1]), dim=1) - x
@@ -155,7 +205,10 @@ class RWKV_Tmix_x070(nn.Module):
         kk = F.normalize(kk.view(B, T, H, -1), dim=-1, p=2.0).view(B, T, C)
         k = k * (1 + (a - 1) * self.k_a)
 
-        if layout is not None:
+        s_end = None
+        if carry is not None:
+            x, s_end = RUN_CUDA_RWKV7g_state(r, w, k, v, -kk, kk * a, _carry_state0(self, carry[1], B, x))
+        elif layout is not None:
             x = RUN_CUDA_RWKV7g_packed(r, w, k, v, -kk, kk * a, layout)
         elif state is None and getattr(self, "time_state", None) is not None:
             x, _ = RUN_CUDA_RWKV7g_state(r, w, k, v, -kk, kk * a, self.wkv_initial_state())
@@ -167,6 +220,8 @@ class RWKV_Tmix_x070(nn.Module):
         x = x + ((r.view(B, T, H, -1) * k.view(B, T, H, -1) * self.r_k).sum(dim=-1, keepdim=True)
                  * v.view(B, T, H, -1)).view(B, T, C)
         x = self.output(x * g)
+        if carry is not None:
+            return x, v_first, (x_last, s_end)
         return x, v_first
 
 
@@ -187,20 +242,28 @@ class RWKV_CMix_x070(nn.Module):
         self.key.weight.data.uniform_(-0.5 / (C ** 0.5), 0.5 / (C ** 0.5))
         self.value.weight.data.zero_()
 
-    def forward(self, x, state=None, layout=None):
-        if getattr(self.args, "fused", False) and x.is_cuda and layout is None:
+    def forward(self, x, state=None, layout=None, carry=None):
+        """carry (training across a cut): a 1-tuple (ffn_x,) entering this segment (ffn_x may be None); returns (out, ffn_x leaving it)."""
+        if carry is not None and (state is not None or layout is not None):
+            raise NotImplementedError("a training carry together with an inference state or packed rows")
+        if getattr(self.args, "fused", False) and x.is_cuda and layout is None and carry is None:
             from . import fused
             if state is None:
                 return fused.cmix_forward(self, x)
             if not torch.is_grad_enabled() and x.dtype == torch.bfloat16:
                 return fused.cmix_forward_stateful(self, x, state)
-        if state is None:
+        x_last = x[:, -1]
+        if carry is not None:
+            xx = time_shift(x, None, carry[0]) - x
+        elif state is None:
             xx = time_shift(x, layout) - x
         else:
             xx = torch.cat((state.ffn_x[self.layer_id].unsqueeze(1), x[:, :-1]), dim=1) - x
             state.ffn_x[self.layer_id].copy_(x[:, -1])
         k = x + xx * self.x_k
         k = torch.relu(self.key(k)) ** 2
+        if carry is not None:
+            return self.value(k), x_last
         return self.value(k)
 
 
@@ -218,9 +281,17 @@ class Block(nn.Module):
         self.att = RWKV_Tmix_x070(args, layer_id)
         self.ffn = RWKV_CMix_x070(args, layer_id)
 
-    def forward(self, x, v_first, state=None, layout=None):
+    def forward(self, x, v_first, state=None, layout=None, carry=None):
+        """carry (training across a cut): this layer's (att_x, ffn_x, S) of a TrainCarry; returns (x, v_first, the layer's next carry)."""
         if self.layer_id == 0:
             x = self.ln0(x)
+        if carry is not None:
+            if state is not None or layout is not None:
+                raise NotImplementedError("a training carry together with an inference state or packed rows")
+            xx, v_first, (att_x, s_end) = self.att(self.ln1(x), v_first, None, None, (carry[0], carry[2]))
+            x = x + xx
+            xx, ffn_x = self.ffn(self.ln2(x), None, None, (carry[1],))
+            return x + xx, v_first, (att_x, ffn_x, s_end)
         if layout is not None:
             xx, v_first = self.att(self.ln1(x), v_first, None, layout)
             x = x + xx
@@ -253,6 +324,25 @@ class L2Wrap(torch.autograd.Function):
         gy = torch.zeros_like(y)
         gy.scatter_(-1, ids, maxx * factor)
         return grad_output, gy
+
+
+class L2WrapWindow(torch.autograd.Function):
+    """L2Wrap on the logits of a window of a longer row (VisualRWKV.train_step_cut): the same gradient term with the factor of the whole
+    row, 1e-4 / (B * T of the uncut row), passed in."""
+
+    @staticmethod
+    def forward(ctx, loss, y, factor):
+        ctx.save_for_backward(y)
+        ctx.factor = float(factor)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        y = ctx.saved_tensors[0]
+        maxx, ids = torch.max(y, -1, keepdim=True)
+        gy = torch.zeros_like(y)
+        gy.scatter_(-1, ids, maxx * ctx.factor)
+        return grad_output, gy, None
 
 
 class RWKV7State:
@@ -322,10 +412,13 @@ class RWKV(nn.Module):
     def unpad(self, x, num_tokens_to_pad):
         return x[:, num_tokens_to_pad:] if num_tokens_to_pad > 0 else x
 
-    def forward_features(self, x, layout=None):
+    def forward_features(self, x, layout=None, carry=None):
         """Everything up to (not including) the head; returns (hidden, num_tokens_to_pad).  layout: a wkv7.PackedLayout for packed rows
-        (T is then a multiple of CHUNK_LEN by construction: no left pad)."""
+        (T is then a multiple of CHUNK_LEN by construction: no left pad).  carry: a TrainCarry when x is one segment of a longer row (T a
+        multiple of CHUNK_LEN: a left pad inside a row would change it); returns (hidden, 0, the carry leaving the segment)."""
         args = self.args
+        if carry is not None:
+            return self._forward_features_carry(x, layout, carry)
         if layout is not None:
             layout.check(x.size(0), x.size(1), x.device)
             if getattr(args, "state_tune", 0):
@@ -363,9 +456,46 @@ class RWKV(nn.Module):
                 x, v_first = block(x, v_first)
         return self.ln_out(x), num_tokens_to_pad
 
-    def forward(self, x, hidden_only=False, layout=None):
+    def _forward_features_carry(self, x, layout, carry):
+        args = self.args
+        if layout is not None:
+            raise NotImplementedError("a training carry together with packed rows: the segments of a packed row would each need their own")
+        if x.size(1) % CHUNK_LEN != 0:
+            raise ValueError(f"a segment of a cut row must be a multiple of {CHUNK_LEN} tokens (got {x.size(1)})")
+        if len(carry.layers) != len(self.blocks):
+            raise ValueError(f"the carry has {len(carry.layers)} layers, the model {len(self.blocks)}")
+        if args.dropout > 0:
+            x = self.drop0(x)
+        grad_cp = int(args.grad_cp) if torch.is_grad_enabled() else 0
+        if getattr(args, "fused", False):
+            from . import fused
+            if fused.carry_supported(x):
+                h, nxt = fused.blocks_forward(self, x, grad_cp=grad_cp, carry=carry)
+                return h, 0, nxt
+        # the unfused Blocks (the shift in PyTorch, the WKV7 state op): CPU tensors, args.fused off, the two-kernel shift, C > 4096
+        v_first = torch.empty_like(x)
+        layers = []
+        for i, block in enumerate(self.blocks):
+            if grad_cp >= 1:
+                from torch.utils.checkpoint import checkpoint
+                x, v_first, lc = checkpoint(block, x, v_first, None, None, carry[i], use_reentrant=False)
+            else:
+                x, v_first, lc = block(x, v_first, None, None, carry[i])
+            layers.append(lc)
+        return self.ln_out(x), 0, TrainCarry(len(layers), layers)
+
+    def forward(self, x, hidden_only=False, layout=None, carry=None):
         """Logits (B, T, V); hidden_only: forward_features(x) instead (through the module call, so that forward pre-hooks run).
-        layout: a wkv7.PackedLayout when the rows hold several samples end to end."""
+        layout: a wkv7.PackedLayout when the rows hold several samples end to end.
+        carry: a TrainCarry when x is one segment of a longer row; returns (logits, next carry), or forward_features' triple."""
+        if carry is not None:
+            if hidden_only:
+                return self.forward_features(x, layout, carry)
+            x, _, nxt = self.forward_features(x, layout, carry)
+            if x.is_cuda and getattr(self.args, "fused", False):
+                from . import fused
+                return fused.linear(self.head, x), nxt
+            return self.head(x), nxt
         if hidden_only:
             return self.forward_features(x, layout)
         x, num_tokens_to_pad = self.forward_features(x, layout)

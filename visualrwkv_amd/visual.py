@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 from torch.nn import functional as F
 
-from .rwkv7 import IGNORE_INDEX, IMAGE_TOKEN_INDEX, L2Wrap, RWKV
+from .rwkv7 import IGNORE_INDEX, IMAGE_TOKEN_INDEX, L2Wrap, L2WrapWindow, RWKV, TrainCarry
 from .vit import SamDinoSigLIPViTBackbone
 
 
@@ -181,10 +181,24 @@ class VisualRWKV(nn.Module):
         return self.rwkv(x), targets
 
     @staticmethod
-    def loss_from_logits(logits, targets, layout=None):
+    def loss_from_logits(logits, targets, layout=None, window=None):
         """Shifted CE, summed per sample over valid labels / max(valid,1), batch mean, wrapped in L2Wrap
         (src/model.py:418-434).  With a layout "sample" means segment of a packed row: the last row of a segment has no target, the mean
-        runs over layout.n_samples; L2Wrap keeps the reference's formula on the packed (B, T) logits."""
+        runs over layout.n_samples; L2Wrap keeps the reference's formula on the packed (B, T) logits.
+        window = (a, b) (train_step_cut): logits (B, b-a, V) are rows a .. b-1 of the (B, T) row `targets`; the result is their share of the
+        row's loss -- row b-1 predicts token b, a row weighs 1 / (valid labels of its whole sample * B), L2Wrap's factor counts B * T."""
+        if window is not None:
+            if layout is not None:
+                raise NotImplementedError("loss_from_logits: a window of a packed row")
+            a, b = window
+            B, T = targets.shape
+            shift = torch.full_like(targets, IGNORE_INDEX)
+            shift[:, :-1] = targets[:, 1:]
+            valid = (shift != IGNORE_INDEX).sum(1).clamp(min=1)
+            lab = shift[:, a:b].reshape(-1)
+            loss = F.cross_entropy(logits.reshape(-1, logits.size(-1)), lab, ignore_index=IGNORE_INDEX, reduction="none")
+            loss = (loss.view(B, b - a).sum(1) / valid).mean()
+            return L2WrapWindow.apply(loss, logits, 1e-4 / (B * T))
         shift_logits = logits[..., :-1, :].contiguous()
         shift_labels = targets[..., 1:].contiguous()
         if layout is not None:
@@ -241,6 +255,88 @@ class VisualRWKV(nn.Module):
             if fused.ce_supported(logits):
                 return fused.loss_from_logits(logits, targets, IGNORE_INDEX)
         return self.loss_from_logits(logits, targets)
+
+    def _segment_loss(self, h, targets, window):
+        """The share of the row's loss that the hidden state h (B, b-a, C) of rows window = (a, b) carries (see loss_from_logits)."""
+        if getattr(self.args, "fused", False):
+            from . import fused
+            if fused.head_loss_supported(self.rwkv.head, targets, h):
+                return fused.head_loss(self.rwkv.head, h, fused.HeadPlan(targets, 0, IGNORE_INDEX, None, window))
+            if h.is_cuda:
+                return self.loss_from_logits(fused.linear(self.rwkv.head, h), targets, None, window)
+        return self.loss_from_logits(self.rwkv.head(h), targets, None, window)
+
+    def train_step_cut(self, batch, seg_len, truncate=False):
+        """One training step on rows cut into segments of seg_len tokens: forward AND backward.  Gradients are left in `.grad`, the detached
+        loss is returned.  Activation memory is that of one segment; what crosses a cut is a rwkv7.TrainCarry (two token rows and the WKV
+        state per layer).
+        Exact mode: the loss and the gradients of `training_step(batch).backward()` on the uncut rows, for one more forward pass --
+        the segments run forward once without a graph to record the carry entering each; then, last segment first, each is run again
+        from its carry with a graph, and its share of the loss and its outgoing carry (with the gradients the segment after it sent back)
+        are back-propagated together.  The embedding (tokens, image features, projector) is formed once and back-propagated once.
+        truncate=True: truncated back-propagation through time -- one pass, every segment starts from the detached carry of the one
+        before: no gradient crosses a cut, nothing is recomputed."""
+        if batch.get("seg_lens") is not None:
+            raise NotImplementedError("train_step_cut: packed rows (a batch with seg_lens) cannot be cut")
+        targets = batch["labels"]
+        B, T = targets.shape
+        seg_len = int(seg_len)
+        if T % 16 != 0 or seg_len <= 0 or seg_len % 16 != 0:
+            raise ValueError(f"train_step_cut: T ({T}) and seg_len ({seg_len}) must be multiples of 16")
+        bounds = [(a, min(a + seg_len, T)) for a in range(0, T, seg_len)]
+        n_layer = len(self.rwkv.blocks)
+        from contextlib import nullcontext
+        engine = next((p._vrwkv_engine() for p in self.parameters() if getattr(p, "_vrwkv_engine", None) is not None), None)      # dp.Zero1Engine
+        with (engine.hold_reductions() if engine is not None else nullcontext()):
+            x, _ = self.preparing_embedding(batch)
+            xd = x.detach()
+            gx = torch.zeros_like(xd) if x.requires_grad else None
+            total = None
+
+            def run(i, carry, want_grad):
+                a, b = bounds[i]
+                xs = xd[:, a:b].contiguous()
+                if want_grad and gx is not None:
+                    xs.requires_grad_(True)
+                h, _, nxt = self.rwkv(xs, hidden_only=True, carry=carry)
+                return xs, h, nxt
+
+            if truncate:
+                carry = TrainCarry(n_layer)
+                for i, win in enumerate(bounds):
+                    xs, h, nxt = run(i, carry, True)
+                    loss = self._segment_loss(h, targets, win)
+                    loss.backward()
+                    if gx is not None:
+                        gx[:, win[0]:win[1]] = xs.grad
+                    total = loss.detach() if total is None else total + loss.detach()
+                    carry = nxt.detach()
+            else:
+                carries = [TrainCarry(n_layer)]                          # the carry entering every segment
+                with torch.no_grad():
+                    for i in range(len(bounds) - 1):
+                        carries.append(run(i, carries[-1], False)[2].detach())
+                g_out = None                                             # gradients of the carry leaving segment i, from segment i + 1
+                for i in reversed(range(len(bounds))):
+                    cin = carries[i].detach(requires_grad=True) if i > 0 else carries[0]
+                    xs, h, nxt = run(i, cin, True)
+                    loss = self._segment_loss(h, targets, bounds[i])
+                    roots, grads = [loss], [None]
+                    if g_out is not None:
+                        for t, g in zip(nxt.tensors(), g_out):
+                            if g is not None and t.requires_grad:
+                                roots.append(t)
+                                grads.append(g.to(t.dtype))
+                    torch.autograd.backward(roots, grads)
+                    g_out = [t.grad for t in cin.tensors()] if i > 0 else None
+                    if gx is not None:
+                        gx[:, bounds[i][0]:bounds[i][1]] = xs.grad
+                    total = loss.detach() if total is None else total + loss.detach()
+                    carries[i] = None
+                    del xs, h, nxt, loss, roots, grads, cin
+            if gx is not None:
+                x.backward(gx)
+        return total
 
     @torch.no_grad()
     def generate(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx):
