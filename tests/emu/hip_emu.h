@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <vector>
 
 struct dim3 {
@@ -61,7 +62,7 @@ namespace emu {
 
 struct Fiber {
     ucontext_t ctx;
-    std::vector<char> stack;
+    std::unique_ptr<char[]> stack;      // allocated once per launch and left uninitialised: makecontext sets up what a fiber reads
     bool done = false;
 };
 
@@ -123,20 +124,24 @@ void launch(dim3 grid, dim3 block, F&& body, size_t stack_bytes = 256 * 1024) {
     st.body = body;
     st.xchg.assign((size_t)st.nthreads * 16, 0);
     bdim() = block; gdim() = grid;
+    // one set of stacks for all workgroups of the launch.  A fresh zero-filled set per workgroup cost 256 KiB of memset per GPU thread,
+    // which dominates launches of many workgroups with little work each: colsum over 6 x 8192 columns is 3072 workgroups of 256 threads,
+    // 200 GB of memset.  Measured with tests/test_glue_shapes.py on the emulator: test_mix[emu-lb1024_full-M6+dup3] 53.7 s -> 4.6 s, the
+    // slowest case of the module 53.7 s -> 9.5 s (test_post[emu-range_cap]), the module's 99 cases 854 s -> 184 s, with the same results.
+    st.fibers.resize(st.nthreads);
+    for (Fiber& f : st.fibers) f.stack.reset(new char[stack_bytes]);
     for (unsigned bz = 0; bz < grid.z; ++bz)
     for (unsigned by = 0; by < grid.y; ++by)
     for (unsigned bx = 0; bx < grid.x; ++bx) {
         bidx() = emu_uint3{bx, by, bz};
-        st.fibers.clear();
-        st.fibers.resize(st.nthreads);
         st.block_arrived = 0;
         for (int w = 0; w < 32; ++w) st.wave_arrived[w] = 0;
         for (int t = 0; t < st.nthreads; ++t) {
             Fiber& f = st.fibers[t];
-            f.stack.resize(stack_bytes);
+            f.done = false;
             getcontext(&f.ctx);
-            f.ctx.uc_stack.ss_sp = f.stack.data();
-            f.ctx.uc_stack.ss_size = f.stack.size();
+            f.ctx.uc_stack.ss_sp = f.stack.get();
+            f.ctx.uc_stack.ss_size = stack_bytes;
             f.ctx.uc_link = &st.sched;
             makecontext(&f.ctx, (void (*)())trampoline, 0);
         }

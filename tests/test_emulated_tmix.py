@@ -7,7 +7,8 @@ import ctypes
 
 import pytest
 import torch
-import torch.nn.functional as F
+
+from tests.test_glue_shapes import ref_decay, ref_kva, ref_mix
 
 
 L, I, F32 = ctypes.c_long, ctypes.c_int, ctypes.c_float
@@ -52,8 +53,7 @@ def test_mix_forward_backward_against_autograd(emu_lib, B, T, C, M, dup3):
     call(emu_lib, "vrwkv_mix_fwd_bf16", [L, I, I, I, VP, VP, VP, VP], ntok, T, C, M, P(x), PA(mus), PA(outs), None)
     xv = x.double().view(B, T, C).requires_grad_(True)
     mv = [m.double().requires_grad_(True) for m in mus]
-    prev = torch.cat([torch.zeros_like(xv[:, :1]), xv[:, :-1]], dim=1)
-    ref = [(xv + (prev - xv) * m).view(ntok, C) for m in mv]
+    ref = [r.view(ntok, C) for r in ref_mix(xv, mv)]
     for o, r in zip(outs, ref):
         assert torch.equal(o, r.detach().float().bfloat16())          # one fma per element, one rounding
     douts = [bf(ntok, C, g=g) for _ in range(M)]
@@ -137,12 +137,7 @@ def test_kva_forward_backward_against_autograd(emu_lib):
     call(emu_lib, "vrwkv_kva_fwd_bf16", [L, I, I] + [VP] * 14, ntok, C, 1, P(k), P(v), P(vf), P(vl), P(al), P(kk), P(ka), P(a0), P(v0),
          P(k2), P(v2), P(z), P(b), None)
     xs = [t.double().requires_grad_(True) for t in (k, v, vf, vl, al, kk, ka, a0, v0)]
-    kd, vd, vfd, vld, ald, kkd, kad, a0d, v0d = xs
-    a = torch.sigmoid(a0d + ald)
-    v2r = vd + (vfd - vd) * torch.sigmoid(v0d + vld)
-    kkn = F.normalize((kd * kkd).view(ntok, H, -1), dim=-1, p=2.0).view(ntok, C)
-    k2r = kd * (1 + (a - 1) * kad)
-    refs = (k2r, v2r, -kkn, kkn * a)
+    refs = ref_kva(*xs)
     for o, r in zip((k2, v2, z, b), refs):
         assert rel(o, r.detach()) < 3e-3
     grads = [bf(ntok, C, g=g) for _ in range(4)]
@@ -170,4 +165,4 @@ def test_relusq_and_decay(emu_lib):
     assert torch.equal(dh, (2 * torch.relu(h.float()) * dy.float()).bfloat16())
     w0, w = bf(C, g=g), torch.zeros_like(h)
     call(emu_lib, "vrwkv_decay_fwd_bf16", [L, I, VP, VP, VP, VP], n, C, P(h), P(w0), P(w), None)
-    assert rel(w, -F.softplus(-(w0.double() + h.double())) - 0.5) < 3e-3
+    assert rel(w, ref_decay(h.double(), w0.double())) < 3e-3

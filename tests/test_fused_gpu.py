@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle.wkv7_oracle import rel_rms
+from tests.test_glue_shapes import ref_decay, ref_kva, ref_mix, ref_post
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -41,8 +42,7 @@ def test_mix(B, T, C, M):
     gouts = [_rnd(B, T, C, seed=20 + i) for i in range(M)]
 
     def ref(x, *mus):
-        xx = F.pad(x, (0, 0, 1, -1)) - x
-        return tuple(x + xx * m for m in mus)
+        return ref_mix(x, mus)
 
     xs = [x.clone().requires_grad_(True)] + [m.clone().requires_grad_(True) for m in mus]
     outs = fused.mix(*xs)
@@ -64,7 +64,7 @@ def test_decay():
     h = _rnd(2, 17, 256, scale=3.0, seed=3)
     w0 = _rnd(1, 1, 256, scale=2.0, seed=4)
     g = _rnd(2, 17, 256, seed=5)
-    ref = lambda h, w0: -F.softplus(-(w0 + h)) - 0.5
+    ref = ref_decay
     hh, ww = h.clone().requires_grad_(True), w0.clone().requires_grad_(True)
     w = fused.decay(hh, ww)
     w.backward(g)
@@ -77,17 +77,14 @@ def test_decay():
 @pytest.mark.parametrize("has_vres", [False, True])
 def test_kva(has_vres):
     from visualrwkv_amd import fused
-    B, T, C, H = 2, 9, 256, 4
+    B, T, C = 2, 9, 256
     k, v, vf, vl, al = [_rnd(B, T, C, seed=30 + i) for i in range(5)]
     k_k, k_a, a0, v0 = [_rnd(1, 1, C, scale=0.5, seed=40 + i) for i in range(4)]
     gouts = [_rnd(B, T, C, seed=50 + i) for i in range(4)]
 
-    def ref(k, v, vf, vl, al, k_k, k_a, a0, v0):
-        a = torch.sigmoid(a0 + al)
-        v2 = v + (vf - v) * torch.sigmoid(v0 + vl)
-        kk = F.normalize((k * k_k).view(B, T, H, -1), dim=-1, p=2.0).view(B, T, C)
-        k2 = k * (1 + (a - 1) * k_a)
-        return (k2, v2, -kk, kk * a) if has_vres else (k2, -kk, kk * a)
+    def ref(*xs):
+        k2, v2, z, b = [o.view(B, T, C) for o in ref_kva(*[x.view(-1, C) for x in xs])]
+        return (k2, v2, z, b) if has_vres else (k2, z, b)
 
     ins = [k, v, vf, vl, al, k_k, k_a, a0, v0]
     xs = [t.clone().requires_grad_(True) for t in ins]
@@ -116,9 +113,7 @@ def test_post():
     eps = 64e-5
 
     def ref(y, r, k, v, g, ln_w, ln_b, r_k):
-        x = F.group_norm(y.view(B * T, C), H, ln_w, ln_b, eps).view(B, T, C)
-        x = x + ((r.view(B, T, H, -1) * k.view(B, T, H, -1) * r_k).sum(dim=-1, keepdim=True) * v.view(B, T, H, -1)).view(B, T, C)
-        return x * g
+        return ref_post(*[x.view(B * T, C) for x in (y, r, k, v, g)], ln_w, ln_b, r_k, eps).view(B, T, C)
 
     ins = [y, r, k, v, g, ln_w, ln_b, r_k]
     xs = [t.clone().requires_grad_(True) for t in ins]

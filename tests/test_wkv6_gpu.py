@@ -12,6 +12,7 @@ import torch.nn as nn
 from oracle.wkv7_oracle import rel_rms
 from tests.parity import group_bias
 from tests.parity import bf16_close
+from tests.test_glue_shapes import ref_gn_silu, ref_mix
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "v6_ref.pt")
@@ -253,8 +254,7 @@ def test_ddmix_and_gn_silu_kernels_against_fp32():
     torch.autograd.backward(outs, gs)
     got = [o.detach() for o in outs], x.grad.clone(), mm.grad.clone(), [m.grad.clone() for m in mus]
     xf, mmf, musf = x.detach().float().requires_grad_(True), mm.detach().float().requires_grad_(True), [m.detach().float().requires_grad_(True) for m in mus]
-    xx = torch.nn.functional.pad(xf, (0, 0, 1, -1)) - xf
-    ref = [xf + xx * (musf[j] + mmf[j]) for j in range(5)]
+    ref = ref_mix(xf, musf, mmf)
     torch.autograd.backward(ref, [g.float() for g in gs])
     for j in range(5):
         assert rel_rms(got[0][j].float(), ref[j].detach().bfloat16().float()) < 1e-3, j
@@ -273,9 +273,9 @@ def test_ddmix_and_gn_silu_kernels_against_fp32():
     go = torch.randn(B * T, C, device="cuda").bfloat16()
     out.backward(go)
     yf, ggf = y.detach().float().requires_grad_(True), gg.detach().float().requires_grad_(True)
-    lnf = nn.GroupNorm(C // 64, C, eps=64e-5).cuda()
+    lnf = nn.GroupNorm(C // 64, C, eps=64e-5).cuda()                       # holds the fp32 leaves of the reference's weight and bias
     lnf.load_state_dict({k: v.float() for k, v in lnb.state_dict().items()})
-    reff = lnf(yf) * torch.nn.functional.silu(ggf)
+    reff = ref_gn_silu(yf, ggf, lnf.weight, lnf.bias, lnf.eps)
     reff.backward(go.float())
     assert rel_rms(out.detach().float(), reff.detach().bfloat16().float()) < 1e-3
     assert rel_rms(y.grad.float(), yf.grad) < 3e-3 and rel_rms(gg.grad.float(), ggf.grad) < 3e-3
