@@ -39,14 +39,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.parity import NOTES, bf16_close, group_bias
+from tests.shape_checks import Checks
 
 L, I, F32, VP = ctypes.c_long, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 EPS = 64e-5
 TOL = 1e-3
 FLIP = {"emu": 3.7e-3, "hip": 3.7e-3}         # 4 x observed (module docstring)
 PERR = {"emu": 6.1e-6, "hip": 5.1e-6}
-WORST = {b: {"flip": (0.0, ""), "perr": (0.0, "")} for b in FLIP}
 
 BACKENDS = ["emu", pytest.param("hip", marks=pytest.mark.gpu)]      # host lockstep emulator | product library on the MI355X
 #   id                (B, T) of mix / ddmix;  ntok = B T for the rest          C     what it reaches
@@ -217,38 +216,10 @@ def same_bits(a, b):
         assert torch.equal(bits(a[name]), bits(b[name])), f"{name}: the second call differs"
 
 
-def note(be, kind, val, name):
-    if val > WORST[be.name][kind][0]:
-        WORST[be.name][kind] = (val, name)
-    if NOTES:
-        w = WORST[be.name]
-        print(f"[glue] {be.name} {name}: {kind} {val:.3e}   (worst so far: flip {w['flip'][0]:.3e} {w['flip'][1]}, perr {w['perr'][0]:.3e} {w['perr'][1]})")
+CHECKS = Checks("glue", FLIP, PERR, TOL)
+note, act, par = CHECKS.note, CHECKS.act, CHECKS.par
 
 
-def act(be, got, ref, name):
-    """An activation or activation gradient (rows without the guard) against the fp64 reference rounded once to bf16."""
-    x = got[:-1].reshape(-1)
-    rr = ref.detach().reshape(-1).float().bfloat16()
-    assert x.shape == rr.shape, (name, x.shape, rr.shape)
-    note(be, "flip", float((x.float() != rr.float()).float().mean()), name)
-    bf16_close(x, ref, name, tol=TOL, max_flip=FLIP[be.name])
-
-
-def par(be, got, ref, name):
-    """One fp32 parameter-gradient vector (C) against the fp64 reference."""
-    g, r = got.double().cpu(), ref.detach().double().cpu()
-    rms = float(r.pow(2).mean().sqrt())
-    if rms == 0.0:
-        assert not bool(g.any()), f"{name}: the reference is zero"
-        return
-    err = float((g - r).abs().max()) / rms
-    note(be, "perr", err, name)
-    c = int((g - r).abs().argmax())
-    assert err < PERR[be.name], f"{name}: max_c |got - ref| / rms(ref) = {err:.3e} at channel {c} (got {float(g[c]):.6e}, ref {float(r[c]):.6e})"
-    group_bias(g, r, name)
-
-
-# ------------------------------------------------------------------------------------------------ mix
 def _mix_case(be, sid, M, dup3, dd):
     B, T, C = be.shape(sid)
     ntok = B * T
