@@ -190,6 +190,30 @@ int vrwkv_ln_mix_bwd_carry_bf16(long ntok, int T, int C, int M, const void* xn, 
 int vrwkv_mix_bwd_ln_carry_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
                                 const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* y_prev,
                                 const float* dy_last, float* dy_prev, void* dx, float* dmu, float* ws, void* stream);
+/* Modality-routed channel mix (M = 1): a Block with a second LayerNorm and channel mix for image tokens (ln_v / ffn_v,
+ * VisualRWKV-v7/v7.10/src/model.py:233-262) ends in  x + where(mask, ffn_v(ln_v(x)), ffn(ln2(x))).  After the token shift a channel mix is per row, so each
+ * row goes through ONE expert: e = 0 (text: w[0], b[0], mu[0] = ln2, ffn.x_k) where sel[n] == 0, e = 1 (image: w[1], b[1], mu[1] = ln_v, ffn_v.x_k) else.
+ *   forward : xn = bf16(x + delta), mean, rstd in token order, as vrwkv_ln_mix_fwd_packed_bf16 writes them (one set: the statistics are xn's alone);
+ *             out[pos[n]] = y + (y_prev - y) mu_e,  y = bf16(LN_e(xn[n])),  y_prev = bf16(LN_e(xn[n-1])) under ROW n's expert (zeros where n % T == 0 or
+ *             first[n] != 0): bit for bit row n of vrwkv_ln_mix_fwd_packed_bf16 run on the whole input with expert e's parameters.
+ *   backward: dout (ntok, C) in pos order; dx (ntok, C) in token order = dres + one LayerNorm backward of
+ *             w_e(n) dout[n] (1 - mu_e(n)) + w_e(n+1) dout[n+1] mu_e(n+1); dwb (2, 2, C) fp32 = (dgamma, dbeta) of expert 0, then of expert 1, each term
+ *             credited to the expert it came through; dmu (2, C) fp32.  Written, not accumulated: an expert without rows gets zeros.  With one
+ *             expert on every row and pos the identity, dx and that expert's dwb / dmu are those of vrwkv_ln_mix_bwd_packed_bf16 bit for bit.
+ * w, b, mu: arrays of 2 device pointers (C bf16 each).  sel, first: ntok bytes on the device, read as aligned 32-bit words (up to 3 bytes around the
+ * array are read and ignored; every device allocation holds them); first may be NULL.  pos: a permutation of 0 .. ntok-1, ntok int32 (pos_bytes = 4) or
+ * int64 (8).  C % 64 == 0, C <= 4096.  ws: vrwkv_ln_mix_routed_ws_floats(ntok, C) floats.  Deterministic, no atomics. */
+long vrwkv_ln_mix_routed_ws_floats(long ntok, int C);
+int vrwkv_ln_mix_routed_fwd_bf16(long ntok, int T, int C, float eps, const void* x, const void* delta, const void* const* w, const void* const* b,
+                                 const void* const* mu, void* xn, void* out, float* mean, float* rstd, const unsigned char* first,
+                                 const unsigned char* sel, const void* pos, int pos_bytes, void* stream);
+int vrwkv_ln_mix_routed_bwd_bf16(long ntok, int T, int C, const void* xn, const float* mean, const float* rstd, const void* const* w,
+                                 const void* const* b, const void* const* mu, const void* dout, const void* dres, const unsigned char* first,
+                                 const unsigned char* sel, const void* pos, int pos_bytes, void* dx, float* dwb, float* dmu, float* ws,
+                                 void* stream);
+/* dst[i] = src[idx[i]], i < n, rows of C bf16 (C % 8 == 0); idx: n int32 (idx_bytes = 4) or int64 (8) on the device, each a row of src.  The routed
+ * channel mix's way back to token order (idx = pos) and, with the inverse permutation, that step's backward. */
+int vrwkv_row_gather_bf16(long n, int C, const void* src, const void* idx, int idx_bytes, void* dst, void* stream);
 /* Inference form for the frozen ViT towers: xn = x + delta * dscale (dscale = LayerScale gamma (C) bf16 or NULL; delta NULL: no
  * add, xn not written), y = LayerNorm(xn); no statistics kept (timm blocks via src/vision.py:123-134, src/sam.py:231-247). */
 int vrwkv_add_ln_scaled_fwd_bf16(long ntok, int C, float eps, const void* x, const void* delta, const void* dscale, const void* w,

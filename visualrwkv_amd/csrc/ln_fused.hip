@@ -244,4 +244,73 @@ int vrwkv_ln_mix_bwd_carry_bf16(long ntok, int T, int C, int M, const void* xn, 
     return e == hipSuccess ? VRWKV_OK : (int)e;
 }
 
+// Modality-routed channel mix (a Block with ln_v / ffn_v for image tokens, VisualRWKV-v7/v7.10/src/model.py:233-262): every row goes through ONE
+// of two experts, sel[n] == 0 -> (w[0], b[0], mu[0]) (text: ln2, ffn.x_k), else -> (w[1], b[1], mu[1]) (image: ln_v, ffn_v.x_k).  xn, mean and rstd
+// stay in token order; out[pos[n]] = y + (y_prev - y) mu_e with y = LN_e(xn[n]), y_prev = LN_e(xn[n-1]) under row n's expert e (zeros where
+// n % T == 0 or first[n] != 0).  pos: ntok int32 (pos_bytes 4) or int64 (8), a permutation of 0 .. ntok-1; first may be NULL.
+int vrwkv_ln_mix_routed_fwd_bf16(long ntok, int T, int C, float eps, const void* x, const void* delta, const void* const* w, const void* const* b,
+                                 const void* const* mu, void* xn, void* out, float* mean, float* rstd, const unsigned char* first,
+                                 const unsigned char* sel, const void* pos, int pos_bytes, void* stream) {
+    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !x || !w || !b || !mu || !out || !mean || !rstd || !sel || !pos || (delta && !xn)) return VRWKV_EINVAL;
+    if (!w[0] || !w[1] || !b[0] || !b[1] || !mu[0] || !mu[1] || (pos_bytes != 4 && pos_bytes != 8)) return VRWKV_EINVAL;
+    if (!ln_ok(C) || C > 4096) return VRWKV_ESHAPE;
+    LmPtrs pm{}; LmOuts po{};
+    pm.p[0] = (const uint16_t*)mu[0]; po.p[0] = (uint16_t*)out;
+    const LmRoute rt{(const uint16_t*)w[1], (const uint16_t*)b[1], (const uint16_t*)mu[1], sel, pos, pos_bytes == 8};
+    const dim3 grid(ln_grid(ntok, LN_MIX_ROWS_PER_WG)), block(ln_threads(C));
+    hipStream_t st = (hipStream_t)stream;
+#define LN_MIX_FWD_ROUTED(PK) hipLaunchKernelGGL((ln_mix_fwd_kernel<1, PK, false, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, \
+        (const uint16_t*)delta, (const uint16_t*)w[0], (const uint16_t*)b[0], (uint16_t*)xn, mean, rstd, pm, po, first, (const uint16_t*)nullptr,    \
+        (uint16_t*)nullptr, rt)
+    if (first) LN_MIX_FWD_ROUTED(true); else LN_MIX_FWD_ROUTED(false);
+#undef LN_MIX_FWD_ROUTED
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VRWKV_OK : (int)e;
+}
+
+// its backward: dout (ntok, C) in pos order; dx (ntok, C) in token order = dres + LN'(..) with the row's shared statistics; dwb (2, 2, C) fp32 =
+// (dgamma, dbeta) of expert 0, then of expert 1; dmu (2, C) fp32; all written, not accumulated (an expert without rows gets zeros).
+// ws: vrwkv_ln_mix_routed_ws_floats(ntok, C) floats.  Deterministic: per-workgroup partial rows summed in a fixed order.
+long vrwkv_ln_mix_routed_ws_floats(long ntok, int C) { return (long)ln_mix_bwd_grid(ntok) * 6 * C; }
+
+int vrwkv_ln_mix_routed_bwd_bf16(long ntok, int T, int C, const void* xn, const float* mean, const float* rstd, const void* const* w,
+                                 const void* const* b, const void* const* mu, const void* dout, const void* dres, const unsigned char* first,
+                                 const unsigned char* sel, const void* pos, int pos_bytes, void* dx, float* dwb, float* dmu, float* ws,
+                                 void* stream) {
+    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !xn || !mean || !rstd || !w || !b || !mu || !dout || !sel || !pos || !dx || !dwb || !dmu || !ws) return VRWKV_EINVAL;
+    if (!w[0] || !w[1] || !b[0] || !b[1] || !mu[0] || !mu[1] || (pos_bytes != 4 && pos_bytes != 8)) return VRWKV_EINVAL;
+    if (!ln_ok(C) || C > 4096) return VRWKV_ESHAPE;
+    LmPtrs pm{}, pd{};
+    pm.p[0] = (const uint16_t*)mu[0]; pd.p[0] = (const uint16_t*)dout;
+    const LmRoute rt{(const uint16_t*)w[1], (const uint16_t*)b[1], (const uint16_t*)mu[1], sel, pos, pos_bytes == 8};
+    const int G = ln_mix_bwd_grid(ntok);
+    const dim3 grid(G), block(ln_threads(C));
+    hipStream_t st = (hipStream_t)stream;
+    float* part_ln = ws; float* part_mu = ws + (size_t)G * 4 * C;
+#define LN_MIX_BWD_ROUTED_LB(LB, PK) hipLaunchKernelGGL((ln_mix_bwd_kernel<1, false, LB, PK, false, true>), grid, block, 0, st, ntok, T, C, (const uint16_t*)xn, mean, \
+        rstd, (const uint16_t*)w[0], (const uint16_t*)b[0], pm, pd, (const uint16_t*)nullptr, (const uint16_t*)dres, (uint16_t*)dx, part_ln, part_mu, first,        \
+        (const uint16_t*)nullptr, (const float*)nullptr, (float*)nullptr, rt)
+#define LN_MIX_BWD_ROUTED(PK) do { if (block.x <= 256) LN_MIX_BWD_ROUTED_LB(256, PK); else LN_MIX_BWD_ROUTED_LB(512, PK); } while (0)
+    if (first) LN_MIX_BWD_ROUTED(true); else LN_MIX_BWD_ROUTED(false);
+#undef LN_MIX_BWD_ROUTED
+#undef LN_MIX_BWD_ROUTED_LB
+    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(4L * C / 16)), dim3(256), 0, st, G, 4L * C, part_ln, dwb);
+    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, st, G, 2L * C, part_mu, dmu);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VRWKV_OK : (int)e;
+}
+
+// dst[i] = src[idx[i]] for i < n on rows of C bf16 (C % 8 == 0); idx: n int32 (idx_bytes 4) or int64 (8) on the device, every entry a row of src
+int vrwkv_row_gather_bf16(long n, int C, const void* src, const void* idx, int idx_bytes, void* dst, void* stream) {
+    if (n <= 0 || !src || !idx || !dst || (idx_bytes != 4 && idx_bytes != 8)) return VRWKV_EINVAL;
+    if (C <= 0 || C % 8 != 0) return VRWKV_ESHAPE;
+    const long nvec = n * (C / 8);
+    const long g = (nvec + 255) / 256;
+    const dim3 grid((unsigned)(g > (1L << 20) ? (1L << 20) : g)), block(256);
+    if (idx_bytes == 8) hipLaunchKernelGGL(row_gather_kernel<true>, grid, block, 0, (hipStream_t)stream, nvec, C / 8, (const uint16_t*)src, idx, (uint16_t*)dst);
+    else hipLaunchKernelGGL(row_gather_kernel<false>, grid, block, 0, (hipStream_t)stream, nvec, C / 8, (const uint16_t*)src, idx, (uint16_t*)dst);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VRWKV_OK : (int)e;
+}
+
 }  // extern "C"

@@ -225,13 +225,41 @@ struct LmOuts { uint16_t* p[6]; };
 // CARRY (the _carry entries: a row cut into segments that are trained one after the other): y_prev (B, C) bf16 = the LayerNorm output of the row
 // before each sample's first row, in place of the zeros at n % T == 0; y_last (B, C) bf16 receives the LayerNorm output of each sample's last
 // row (what `prev` holds after it).  Either may be NULL; with CARRY off neither is read.
-template <int M, bool PK = false, bool CARRY = false>
+// ROUTED (the _routed entries, M = 1: a Block with a second LayerNorm + channel mix for image tokens, VisualRWKV-v7/v7.10/src/model.py:233-262):
+// sel[n] != 0 sends row n through expert 1 = (w1, b1, mu1), else through expert 0 = the kernel's own (w, b, mu.p[0]).  The statistics of a row
+// belong to xn alone; its lerp reads the row before under ITS expert, LN_e(n)(xn[n-1]), whatever expert that row went through itself.
+// pos[n] (int32, or int64 with pos64) is the row of token n in the routed tensor: where the forward writes out, where the backward reads dout.
+// One byte of sel (and of first_tok) per 2 C-byte row, at a wave-uniform address: read as a scalar.  With ROUTED off nothing of this is read.
+struct LmRoute {
+    const uint16_t *w1, *b1, *mu1;
+    const unsigned char* sel;
+    const void* pos;
+    int pos64;
+};
+// wkv7::uniform_flag_u8 (wkv7_kernels.h) with a 64-bit index; repeated here because the emulator compiles this header inside a namespace of its own
+DEVFN unsigned uniform_flag_u8(const unsigned char* flags, long idx) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned long long a = (unsigned long long)(uintptr_t)(flags + idx);
+    typedef __attribute__((address_space(4))) const unsigned* const_u32_ptr;
+    const unsigned word = *(const_u32_ptr)(a & ~3ull);
+    return __builtin_amdgcn_readfirstlane((word >> (8u * ((unsigned)a & 3u))) & 0xffu);
+#else
+    return flags[idx];
+#endif
+}
+DEVFN long route_row(const LmRoute& rt, long n) {
+    return rt.pos64 ? reinterpret_cast<const long*>(rt.pos)[n] : (long)reinterpret_cast<const int*>(rt.pos)[n];
+}
+
+template <int M, bool PK = false, bool CARRY = false, bool ROUTED = false>
 __global__ __launch_bounds__(1024) void ln_mix_fwd_kernel(long ntok, int T, int C, float eps, const uint16_t* __restrict__ x,
                                                           const uint16_t* __restrict__ delta, const uint16_t* __restrict__ w,
                                                           const uint16_t* __restrict__ b, uint16_t* __restrict__ xn,
                                                           float* __restrict__ mean, float* __restrict__ rstd, LmPtrs mu, LmOuts out,
                                                           const unsigned char* __restrict__ first_tok = nullptr,
-                                                          const uint16_t* __restrict__ y_prev = nullptr, uint16_t* __restrict__ y_last = nullptr) {
+                                                          const uint16_t* __restrict__ y_prev = nullptr, uint16_t* __restrict__ y_last = nullptr,
+                                                          LmRoute rt = LmRoute()) {
+    static_assert(!ROUTED || (M == 1 && !CARRY), "ROUTED: the channel-mix lerp of an uncut row");
     __shared__ float red[4][MAXW][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int c0 = threadIdx.x * 8;
@@ -243,6 +271,8 @@ __global__ __launch_bounds__(1024) void ln_mix_fwd_kernel(long ntok, int T, int 
     uint4 mp[M];                                                 // lerp weights, packed (unpacked where used: registers)
 #pragma unroll
     for (int j = 0; j < M; ++j) mp[j] = act ? ldg(mu.p[j] + c0) : z4;
+    uint4 w1p = z4, b1p = z4, m1p = z4;                          // ROUTED: expert 1, packed like mp
+    if (ROUTED && act) { w1p = ldg(rt.w1 + c0); b1p = ldg(rt.b1 + c0); m1p = ldg(rt.mu1 + c0); }
     const float inv_c = 1.f / (float)C;
     const long n0 = (lo % T != 0) ? lo - 1 : lo;                 // the row before the range: only its LayerNorm output is needed
     uint4 nx = act ? ldg(x + n0 * C + c0) : z4, nd = (act && delta) ? ldg(delta + n0 * C + c0) : z4;
@@ -278,6 +308,30 @@ __global__ __launch_bounds__(1024) void ln_mix_fwd_kernel(long ntok, int T, int 
         for (int e = 0; e < 8; ++e) { const float t = act ? v.f[e] - mu_ : 0.f; q[0] = fmaf(t, t, q[0]); }
         block_sum<1>(red, par + 1, wave, lane, nw, q);
         const float rs = rsqrtf(q[0] * inv_c + eps);
+        if (ROUTED) {
+            // `prev` carries the normalised row (v - mean) rstd: the LayerNorm output of the row before is re-formed from it under this row's
+            // expert with the operations of the plain kernel, so a row's output has the bits of that kernel run with this expert's parameters
+            V8 xh;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xh.f[e] = (v.f[e] - mu_) * rs;
+            if (own) {
+                const bool img = uniform_flag_u8(rt.sel, n) != 0;
+                const V8 we = img ? unpack8(w1p) : wv, be = img ? unpack8(b1p) : bv, m = unpack8(img ? m1p : mp[0]);
+                const bool first = tpos == 0 || (PK && uniform_flag_u8(first_tok, n) != 0);
+                V8 o, op;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { o.f[e] = fmaf(xh.f[e], we.f[e], be.f[e]); op.f[e] = fmaf(prev.f[e], we.f[e], be.f[e]); }
+                const V8 cur = unpack8(pack8(o)), yp = unpack8(pack8(op));
+                V8 r;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) r.f[e] = fmaf((first ? 0.f : yp.f[e]) - cur.f[e], m.f[e], cur.f[e]);
+                if (act) stg(out.p[0] + route_row(rt, n) * C + c0, pack8(r));
+                if (threadIdx.x == 0) { mean[n] = mu_; rstd[n] = rs; }
+            }
+            prev = xh;
+            if (++tpos == T) tpos = 0;
+            continue;
+        }
         V8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o.f[e] = fmaf((v.f[e] - mu_) * rs, wv.f[e], bv.f[e]);
@@ -329,6 +383,185 @@ DEVFN void ln_row_bwd(float (*red)[MAXW][2], int slot, int wave, int lane, int n
     if (act) stg(dst, pack8(o));
 }
 
+// The ROUTED form of ln_mix_bwd_kernel (M = 1).  Row n's lerp went through expert e(n), so the gradient of the normalised row n collects
+//   w_e(n) dout[n] (1 - mu_e(n))  +  w_e(n+1) dout[n+1] mu_e(n+1)       (the second term: row n+1 read row n under ITS expert)
+// and one LayerNorm backward follows with the row's statistics, which both experts share.  Where e(n) == e(n+1) the two terms are added
+// before the bf16 rounding and the row takes the plain kernel's path, operation for operation; where they differ each term is rounded on
+// its own (two LayerNorm outputs, two gradients) and dw / db take each from the expert it came through.
+// Registers hold the parameters and the partial sums (dw, db, dmu) of ONE expert, the current row's: a workgroup walks its rows in order and
+// an expert change is rare on real rows (one image block per sample).  At a change the sums go to the workgroup's own partial row of that
+// expert (plain vector stores) and the other expert's are taken up again from there, or from zero: one writer per address, a fixed order.
+template <bool PK>
+DEVFN void ln_mix_bwd_routed(float (*red)[MAXW][2], long ntok, int T, int C, const uint16_t* __restrict__ xn, const float* __restrict__ mean,
+                             const float* __restrict__ rstd, const uint16_t* __restrict__ w0, const uint16_t* __restrict__ b0,
+                             const uint16_t* __restrict__ mu0, const uint16_t* __restrict__ dout, const uint16_t* __restrict__ dres,
+                             uint16_t* __restrict__ dx, float* __restrict__ part_ln, float* __restrict__ part_mu,
+                             const unsigned char* __restrict__ first_tok, const LmRoute& rt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int c0 = threadIdx.x * 8;
+    const bool act = c0 < C;
+    const long lo = ntok * blockIdx.x / gridDim.x, hi = ntok * (blockIdx.x + 1) / gridDim.x;
+    const uint4 z4 = make_uint4(0, 0, 0, 0);
+    const int cc = act ? c0 : 0;
+    const float inv_c = 1.f / (float)C;
+    float* pl = part_ln + (size_t)blockIdx.x * 4 * C + cc;       // [expert][dw | db][C]
+    float* pm = part_mu + (size_t)blockIdx.x * 2 * C + cc;       // [expert][C]
+    V8 gw, gb, gm;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { gw.f[e] = 0.f; gb.f[e] = 0.f; gm.f[e] = 0.f; }
+    auto st8 = [&](float* p, const V8& v) {
+        *reinterpret_cast<float4*>(p) = make_float4(v.f[0], v.f[1], v.f[2], v.f[3]);
+        *reinterpret_cast<float4*>(p + 4) = make_float4(v.f[4], v.f[5], v.f[6], v.f[7]);
+    };
+    auto ld8 = [&](const float* p) {
+        const float4 a = *reinterpret_cast<const float4*>(p), c = *reinterpret_cast<const float4*>(p + 4);
+        V8 r;
+        r.f[0] = a.x; r.f[1] = a.y; r.f[2] = a.z; r.f[3] = a.w; r.f[4] = c.x; r.f[5] = c.y; r.f[6] = c.z; r.f[7] = c.w;
+        return r;
+    };
+    auto put_sums = [&](int ex) {
+        if (act) { st8(pl + (size_t)ex * 2 * C, gw); st8(pl + (size_t)ex * 2 * C + C, gb); st8(pm + (size_t)ex * C, gm); }
+    };
+    unsigned stored = 0;                                         // wave-uniform, bit e: has expert e's partial row been written?
+    int ex = 0;
+    if (lo < hi) {
+        ex = uniform_flag_u8(rt.sel, lo) != 0;
+        uint4 wp = z4, bp = z4, mp = z4;
+        auto load_params = [&](int e) {
+            if (act) { wp = ldg((e ? rt.w1 : w0) + c0); bp = ldg((e ? rt.b1 : b0) + c0); mp = ldg((e ? rt.mu1 : mu0) + c0); }
+        };
+        load_params(ex);
+        auto ln_out = [&](uint4 xp, float m0, float r0) {
+            const V8 xv = unpack8(xp), wv = unpack8(wp), bv = unpack8(bp);
+            V8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o.f[e] = fmaf((xv.f[e] - m0) * r0, wv.f[e], bv.f[e]);
+            return unpack8(pack8(o));
+        };
+        V8 aprev;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) aprev.f[e] = 0.f;
+        uint4 xprev = z4, resprev = z4;
+        float muprev = 0.f, rsprev = 0.f;
+        if (lo % T != 0) { xprev = ldg(xn + (lo - 1) * C + cc); muprev = mean[lo - 1]; rsprev = rstd[lo - 1]; }
+        const long last = (hi < ntok && hi % T != 0) ? hi : hi - 1;
+        uint4 nd, nx, nr = z4;
+        float nmu, nrs;
+        nd = ldg(dout + route_row(rt, lo) * C + cc);
+        nx = ldg(xn + lo * C + cc);
+        if (dres) nr = ldg(dres + lo * C + cc);
+        nmu = mean[lo]; nrs = rstd[lo];
+        int slot = 0;
+        int tpos = (int)(lo % T);
+        for (long n = lo; n <= last; ++n) {
+            const bool inside = n < hi, cont = tpos != 0 && !(PK && uniform_flag_u8(first_tok, n) != 0);
+            const int en = uniform_flag_u8(rt.sel, n) != 0;
+            const bool cross = en != ex;                         // n > lo: ex is the expert of row n-1
+            V8 ga = aprev;                                       // (only read after a change of expert)
+            if (cross) {
+                // row n-1's own term leaves through the expert it came through, whose parameters and sums are still in the registers
+                const V8 xv = unpack8(xprev), wv = unpack8(wp), t = unpack8(pack8(aprev));
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float xh = act ? (xv.f[e] - muprev) * rsprev : 0.f;
+                    ga.f[e] = t.f[e] * wv.f[e];
+                    gw.f[e] = fmaf(t.f[e], xh, gw.f[e]);
+                    gb.f[e] += t.f[e];
+                }
+                put_sums(ex);
+                stored |= 1u << ex;
+                ex = en;
+                load_params(ex);
+                if ((stored >> ex) & 1u) { gw = ld8(pl + (size_t)ex * 2 * C); gb = ld8(pl + (size_t)ex * 2 * C + C); gm = ld8(pm + (size_t)ex * C); }
+                else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { gw.f[e] = 0.f; gb.f[e] = 0.f; gm.f[e] = 0.f; }
+                }
+            }
+            keep_packed(wp); keep_packed(bp); keep_packed(mp);
+            const uint4 cx = nx, cr = nr;
+            const float mu_ = nmu, rs = nrs;
+            V8 xx;
+            {
+                const V8 y = ln_out(cx, mu_, rs), yp = ln_out(xprev, muprev, rsprev);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) xx.f[e] = inside ? (cont ? yp.f[e] : 0.f) - y.f[e] : 0.f;
+            }
+            V8 dsum, bvv;
+            {
+                const V8 d = unpack8(nd), m = unpack8(mp);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    dsum.f[e] = 0.f + d.f[e];
+                    bvv.f[e] = fmaf(d.f[e], m.f[e], 0.f);
+                    gm.f[e] = fmaf(d.f[e], xx.f[e], gm.f[e]);
+                }
+            }
+            if (n + 1 <= last) {
+                const long o = (n + 1) * C + cc;
+                nd = ldg(dout + route_row(rt, n + 1) * C + cc);
+                if (n + 1 < hi) {
+                    nx = ldg(xn + o);
+                    if (dres) nr = ldg(dres + o);
+                    nmu = mean[n + 1]; nrs = rstd[n + 1];
+                }
+            }
+            if (n > lo) {
+                V8 xh;
+                const V8 xv = unpack8(xprev);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) xh.f[e] = act ? (xv.f[e] - muprev) * rsprev : 0.f;
+                if (!cross) {                                    // one expert on both sides: the plain kernel's row
+                    V8 t;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) t.f[e] = aprev.f[e] + (cont ? bvv.f[e] : 0.f);
+                    ln_row_bwd(red, slot, wave, lane, nw, act, inv_c, unpack8(wp), unpack8(pack8(t)), xh, rsprev, resprev, gw, gb, dx + (n - 1) * C + cc);
+                } else {                                         // ga = row n-1's own term times its expert's w; row n's term comes through this expert
+                    const V8 wv = unpack8(wp), tb = unpack8(pack8(bvv));
+                    V8 g;
+                    float s[2] = {0.f, 0.f};
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float t = cont ? tb.f[e] : 0.f;
+                        g.f[e] = fmaf(t, wv.f[e], ga.f[e]);
+                        s[0] += g.f[e];
+                        s[1] = fmaf(g.f[e], xh.f[e], s[1]);
+                        gw.f[e] = fmaf(t, xh.f[e], gw.f[e]);
+                        gb.f[e] += t;
+                    }
+                    block_sum<2>(red, slot, wave, lane, nw, s);
+                    const float c1 = s[0] * inv_c, c2 = s[1] * inv_c;
+                    V8 o = unpack8(resprev);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o.f[e] = fmaf(rsprev, g.f[e] - c1 - xh.f[e] * c2, o.f[e]);
+                    if (act) stg(dx + (n - 1) * C + cc, pack8(o));
+                }
+                slot ^= 1;
+            }
+            if (inside) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) aprev.f[e] = dsum.f[e] - bvv.f[e];
+                xprev = cx; resprev = cr; muprev = mu_; rsprev = rs;
+            }
+            if (++tpos == T) tpos = 0;
+        }
+        if (last == hi - 1) {                                    // no successor row: the gradient of the last row is A
+            V8 xh;
+            const V8 xv = unpack8(xprev);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xh.f[e] = act ? (xv.f[e] - muprev) * rsprev : 0.f;
+            ln_row_bwd(red, slot, wave, lane, nw, act, inv_c, unpack8(wp), unpack8(pack8(aprev)), xh, rsprev, resprev, gw, gb, dx + (hi - 1) * C + cc);
+        }
+    }
+    put_sums(ex);
+    if (!((stored >> (ex ^ 1)) & 1u)) {                                       // an expert without a row in this range: zeros
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { gw.f[e] = 0.f; gb.f[e] = 0.f; gm.f[e] = 0.f; }
+        put_sums(ex ^ 1);
+    }
+}
+
+
 // DUP3: output 3 (x_v) has two consumers; their gradients arrive as dout.p[3] and dout3b (see mix_bwd_kernel in tmix_fused.hip).
 // LB: threads per workgroup the instantiation is compiled for (C / 8 rounded up to a wave).  Register discipline (M = 6 keeps 48
 // gradient accumulators per thread): rows travel packed (bf16) and are unpacked where used, the previous row is carried as packed
@@ -337,7 +570,8 @@ DEVFN void ln_row_bwd(float (*red)[MAXW][2], int slot, int wave, int lane, int n
 // CARRY (the _carry entries): y_prev as in the forward; dy_last (B, C) fp32 = the gradient that reaches the LayerNorm output of each sample's
 // last row from the segment after it, added to that row's A in place of a continuing row's Bv; dy_prev (B, C) fp32 receives Bv of each sample's first
 // row, the term that has nowhere to go without a carry.  fp32 both: aprev + Bv is formed in fp32 and rounded once.  Each may be NULL.
-template <int M, bool DUP3, int LB, bool PK = false, bool CARRY = false>
+// ROUTED: see ln_mix_bwd_routed above; dout.p[0] is then in routed row order (rt.pos), part_ln holds (2, 2, C) and part_mu (2, C) per workgroup.
+template <int M, bool DUP3, int LB, bool PK = false, bool CARRY = false, bool ROUTED = false>
 __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long ntok, int T, int C, const uint16_t* __restrict__ xn,
                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
                                                         const uint16_t* __restrict__ w, const uint16_t* __restrict__ b, LmPtrs mu,
@@ -346,8 +580,13 @@ __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long 
                                                         float* __restrict__ part_ln, float* __restrict__ part_mu,
                                                         const unsigned char* __restrict__ first_tok = nullptr,
                                                         const uint16_t* __restrict__ y_prev = nullptr, const float* __restrict__ dy_last = nullptr,
-                                                        float* __restrict__ dy_prev = nullptr) {
+                                                        float* __restrict__ dy_prev = nullptr, LmRoute rt = LmRoute()) {
+    static_assert(!ROUTED || (M == 1 && !DUP3 && !CARRY), "ROUTED: the channel-mix lerp of an uncut row");
     __shared__ float red[2][MAXW][2];
+    if (ROUTED) {
+        ln_mix_bwd_routed<PK>(red, ntok, T, C, xn, mean, rstd, w, b, mu.p[0], dout.p[0], dres, dx, part_ln, part_mu, first_tok, rt);
+        return;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int c0 = threadIdx.x * 8;
     const bool act = c0 < C;
@@ -498,6 +737,18 @@ __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long 
             *reinterpret_cast<float4*>(dm) = make_float4(gm[j].f[0], gm[j].f[1], gm[j].f[2], gm[j].f[3]);
             *reinterpret_cast<float4*>(dm + 4) = make_float4(gm[j].f[4], gm[j].f[5], gm[j].f[6], gm[j].f[7]);
         }
+    }
+}
+
+// dst[i] = src[idx[i]] on rows of C bf16 (cv = C / 8 16-byte pieces per row; idx int32, or int64 with IDX64): the routed channel mix's way back to
+// token order, and with the inverse index that step's backward
+template <bool IDX64>
+__global__ __launch_bounds__(256) void row_gather_kernel(long nvec, int cv, const uint16_t* __restrict__ src, const void* __restrict__ idx,
+                                                         uint16_t* __restrict__ dst) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / cv, c = i - r * cv;
+        const long sr = IDX64 ? reinterpret_cast<const long*>(idx)[r] : (long)reinterpret_cast<const int*>(idx)[r];
+        stg(dst + i * 8, ldg(src + (sr * cv + c) * 8));
     }
 }
 

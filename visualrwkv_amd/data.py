@@ -346,6 +346,9 @@ class DevicePrefetcher:
         for k in ("seg_lens", "n_samples"):                      # packed batches (pack_batches): host lists the model builds its layout from
             if k in batch:
                 out[k] = batch[k]
+        # the image-token count, taken here where the ids are still on the host: args.modality_ffn sizes its two channel-mix GEMMs by it
+        # (fused.RoutePlan) and would otherwise wait for the device in every step
+        out["n_image_tokens"] = int((batch["input_ids"] == IMAGE_TOKEN_INDEX).sum())
         if "images_u8" in batch:
             if batch["images_u8"]:
                 per_tower = {t: [] for t in self.towers}

@@ -776,6 +776,176 @@ class _AddLnMixCarry(torch.autograd.Function):
                 *[dmu[i].view(sh) for i, sh in enumerate(ctx.mu_shapes)])
 
 
+class RoutePlan:
+    """Which expert every token of one batch goes through in a Block with `ffn_v` (args.modality_ffn; VisualRWKV-v7/v7.10/src/model.py:233-262), formed
+    once per batch from the image mask like PackedLayout / HeadPlan and shared by all layers.
+      mask  (B, T, 1) bool, as the reference passes it (already left-padded with False where the rows were padded)
+      sel   (B*T) uint8 on the device: 0 = text (ffn / ln2), 1 = image (ffn_v / ln_v)
+      n_v   the image-token count, a Python int: the row counts of the two experts' GEMMs are host values.  Pass it when the batch was counted on
+            the host (data.DevicePrefetcher puts `n_image_tokens` into every batch before the copy to the device: no synchronisation); None
+            counts the mask here, which waits for the device when the mask lives there.  A passed count is checked against the mask without
+            waiting: the device-side count goes to pinned memory behind an event, like HeadPlan's, and verify() -- called by the first
+            backward that uses the plan, by when the copy has long landed -- raises if the two differ (a wrong count would send rows
+            through the wrong expert without any other sign)
+      pos   (B*T) int32: the row of token n in the routed tensor -- image rows first, then text rows, each group in token order
+      inv   (B*T) int32: the token of routed row i (the inverse of pos)
+    Nothing is cached across batches."""
+
+    def __init__(self, mask, n_v=None):
+        if mask.dtype != torch.bool or mask.dim() not in (2, 3) or (mask.dim() == 3 and mask.shape[-1] != 1):
+            raise ValueError(f"RoutePlan: the mask must be (B, T) or (B, T, 1) bool, got {tuple(mask.shape)} {mask.dtype}")
+        self.mask = mask if mask.dim() == 3 else mask.unsqueeze(-1)
+        self.B, self.T = self.mask.shape[:2]
+        flat = self.mask.reshape(-1)
+        self.ntok = flat.numel()
+        self._pending = None
+        if n_v is None or not flat.is_cuda:
+            count = int(flat.sum())
+            if n_v is not None and int(n_v) != count:
+                raise ValueError(f"RoutePlan: n_v = {int(n_v)}, but the mask holds {count} image tokens")
+            self.n_v = count
+        else:
+            self.n_v = int(n_v)
+            host = torch.empty(1, dtype=torch.long, pin_memory=True)
+            host.copy_(flat.sum().view(1), non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(flat.device))
+            self._pending = (host, ev)
+        if not 0 <= self.n_v <= self.ntok:
+            raise ValueError(f"RoutePlan: n_v = {self.n_v} of {self.ntok} tokens")
+        self.sel = flat.to(torch.uint8).contiguous()
+        order = torch.argsort(~flat, stable=True)                 # image tokens first, each group in token order
+        self.inv = order.to(torch.int32)
+        self.pos = torch.empty_like(self.inv)
+        self.pos[order] = torch.arange(self.ntok, dtype=torch.int32, device=flat.device)
+
+    @property
+    def uniform(self):
+        """One expert takes every row: pos is the identity, nothing has to be brought back into token order."""
+        return self.n_v == 0 or self.n_v == self.ntok
+
+    def verify(self):
+        """A caller-supplied n_v against the mask's own count (see the class docstring); waits for nothing once the copy has landed."""
+        if self._pending is not None:
+            host, ev = self._pending
+            ev.synchronize()
+            self._pending = None
+            if int(host[0]) != self.n_v:
+                raise ValueError(f"RoutePlan: n_v = {self.n_v} was passed in, but the mask holds {int(host[0])} image tokens: "
+                                 "rows went through the wrong expert")
+
+    def check(self, B, T, device):
+        if (self.B, self.T) != (B, T) or self.sel.device != device:
+            raise ValueError(f"RoutePlan: built for ({self.B}, {self.T}) on {self.sel.device}, used with ({B}, {T}) on {device}")
+
+
+class _AddLnMixRouted(torch.autograd.Function):
+    """`_AddLnMix` (M = 1) for a Block with two channel mixes: (xn, k_v, k_t) = (x + delta, the lerp of the image rows under (ln_v, ffn_v.x_k), of the
+    text rows under (ln2, ffn.x_k)), each row through one expert, its shifted value the row before under ITS expert (csrc/ln_fused.hip:
+    vrwkv_ln_mix_routed_*).  k_v (n_v, C) and k_t (ntok - n_v, C) are the two parts of one routed tensor in plan.pos order; x_k: (text, image)."""
+
+    @staticmethod
+    def forward(ctx, x, delta, w_t, b_t, w_v, b_v, eps, plan, first, mu_t, mu_v):
+        B, T, C = x.shape
+        plan.check(B, T, x.device)
+        x = x.contiguous()
+        delta = delta.contiguous() if delta is not None else None
+        ws, bs = [w_t.contiguous(), w_v.contiguous()], [b_t.contiguous(), b_v.contiguous()]
+        mus = [mu_t.reshape(C).contiguous(), mu_v.reshape(C).contiguous()]
+        _chk(x, delta, *ws, *bs, *mus)
+        ntok = B * T
+        xn = torch.empty_like(x) if delta is not None else x
+        out = torch.empty(ntok, C, dtype=x.dtype, device=x.device)
+        mean = torch.empty(ntok, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(ntok, dtype=torch.float32, device=x.device)
+        if first is not None and (first.dtype != torch.uint8 or first.numel() != ntok or first.device != x.device or not first.is_contiguous()):
+            raise ValueError(f"add_ln_mix_routed: `first` must be a contiguous uint8 tensor of {ntok} marks on {x.device}")
+        rc = hip_lib.load().vrwkv_ln_mix_routed_fwd_bf16(ntok, T, C, float(eps), x.data_ptr(), _p(delta), _ptr_array(ws), _ptr_array(bs), _ptr_array(mus),
+                                                         xn.data_ptr() if delta is not None else 0, out.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                         _p(first), plan.sel.data_ptr(), plan.pos.data_ptr(), 4, _stream(x))
+        hip_lib.check(rc, "vrwkv_ln_mix_routed_fwd_bf16")
+        ctx.plan, ctx.first = plan, first
+        ctx.save_for_backward(xn, mean, rstd, *ws, *bs, *mus)
+        ctx.has_delta = delta is not None
+        ctx.mu_shapes = (mu_t.shape, mu_v.shape)
+        return xn, out[:plan.n_v], out[plan.n_v:]
+
+    @staticmethod
+    def backward(ctx, d_xn, d_kv, d_kt):
+        xn, mean, rstd, w_t, w_v, b_t, b_v, mu_t, mu_v = ctx.saved_tensors
+        plan = ctx.plan
+        plan.verify()
+        B, T, C = xn.shape
+        ntok = B * T
+        parts = [d for d, n in ((d_kv, plan.n_v), (d_kt, ntok - plan.n_v)) if n > 0]
+        if any(d is None for d in parts):
+            parts = [d if d is not None else torch.zeros(n, C, dtype=xn.dtype, device=xn.device)
+                     for d, n in ((d_kv, plan.n_v), (d_kt, ntok - plan.n_v)) if n > 0]
+        dout = (parts[0] if len(parts) == 1 else torch.cat(parts)).contiguous()
+        d_xn = d_xn.contiguous() if d_xn is not None else None
+        _chk(d_xn, dout)
+        dx = torch.empty_like(xn)
+        dwb = torch.empty(2, 2, C, dtype=torch.float32, device=xn.device)
+        dmu = torch.empty(2, C, dtype=torch.float32, device=xn.device)
+        lib = hip_lib.load()
+        ws = torch.empty(lib.vrwkv_ln_mix_routed_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
+        rc = lib.vrwkv_ln_mix_routed_bwd_bf16(ntok, T, C, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr_array([w_t, w_v]), _ptr_array([b_t, b_v]),
+                                              _ptr_array([mu_t, mu_v]), dout.data_ptr(), _p(d_xn), _p(ctx.first), plan.sel.data_ptr(), plan.pos.data_ptr(), 4,
+                                              dx.data_ptr(), dwb.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
+        hip_lib.check(rc, "vrwkv_ln_mix_routed_bwd_bf16")
+        dwb = dwb.to(w_t.dtype)
+        dmu = dmu.to(xn.dtype)
+        return (dx, (dx if ctx.has_delta else None), dwb[0, 0], dwb[0, 1], dwb[1, 0], dwb[1, 1], None, None, None,
+                dmu[0].view(ctx.mu_shapes[0]), dmu[1].view(ctx.mu_shapes[1]))
+
+
+def row_gather(src, idx):
+    """src[idx] for (n, C) bf16 rows and an int32 / int64 index on the device (csrc/ln_fused.hip: vrwkv_row_gather_bf16); no autograd."""
+    src = src.contiguous()
+    _chk(src)
+    n, C = idx.numel(), src.shape[-1]
+    out = torch.empty(n, C, dtype=src.dtype, device=src.device)
+    rc = hip_lib.load().vrwkv_row_gather_bf16(n, C, src.data_ptr(), idx.data_ptr(), idx.element_size(), out.data_ptr(), _stream(src))
+    hip_lib.check(rc, "vrwkv_row_gather_bf16")
+    return out
+
+
+class _Unroute(torch.autograd.Function):
+    """The routed tensor (rows in plan.pos order) back in token order: out[n] = routed[pos[n]]; the gradient goes the other way through plan.inv."""
+
+    @staticmethod
+    def forward(ctx, routed, plan):
+        ctx.plan = plan
+        return row_gather(routed, plan.pos)
+
+    @staticmethod
+    def backward(ctx, d):
+        return row_gather(d.reshape(-1, d.shape[-1]), ctx.plan.inv), None
+
+
+def add_ln_mix_routed(x, delta, ln_t, ln_v, x_k_t, x_k_v, plan, first=None):
+    """Returns (x + delta, k_v, k_t) -- see `_AddLnMixRouted`."""
+    if ln_t.eps != ln_v.eps:
+        raise ValueError("add_ln_mix_routed: ln2 and ln_v must share eps (the row statistics are computed once)")
+    return _AddLnMixRouted.apply(x, delta, ln_t.weight, ln_t.bias, ln_v.weight, ln_v.bias, ln_t.eps, plan, first, x_k_t, x_k_v)
+
+
+def cmix_routed(block, x, att_out, plan, first=None, selective=False):
+    """The end of a Block with `ffn_v`: x + att_out, then where(mask, ffn_v(ln_v(.)), ffn(ln2(.))) with every row through its own expert only --
+    one routed add_ln_mix, the two channel mixes on n_v and ntok - n_v rows, and one pass back into token order.  Returns (x + att_out, the
+    channel-mix output still to be added)."""
+    B, T, C = x.shape
+    x, k_v, k_t = add_ln_mix_routed(x, att_out, block.ln2, block.ln_v, block.ffn.x_k, block.ffn_v.x_k, plan, first)
+    parts = []
+    if plan.n_v > 0:
+        parts.append(cmix_from_mixed(block.ffn_v, k_v, recompute_relusq=selective))
+    if plan.n_v < plan.ntok:
+        parts.append(cmix_from_mixed(block.ffn, k_t, recompute_relusq=selective))
+    if plan.uniform:
+        return x, parts[0].view(B, T, C)
+    return x, _Unroute.apply(torch.cat(parts), plan).view(B, T, C)
+
+
 def add_ln_mix(x, delta, ln, mus, dup3=False, first=None, carry=None):
     """Returns (x + delta, [lerp outputs]) -- see `_AddLnMix`.  first: the marks of a wkv7.PackedLayout (layout.first) for packed rows.
     carry: a 1-tuple (y_prev,) when x is one segment of a longer row (y_prev may be None: the row starts here); returns
@@ -813,14 +983,19 @@ def add_ln_supported(x):
     return x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 64 == 0 and x.shape[-1] <= 8192
 
 
-def _block_segment(block, x, delta, v_first, selective=False, layout=None, carry=None):
+def _block_segment(block, x, delta, v_first, selective=False, layout=None, carry=None, route=None):
     """One Block on the (x, pending delta) residual stream: returns (x + delta, ffn output still to be added, v_first).
+    route: a RoutePlan when the Block has `ffn_v` / `ln_v` (args.modality_ffn): image rows take those, text rows ffn / ln2 (cmix_routed).
     selective: the selective-recompute mode of blocks_forward (WKV7 by-products and relu(h)^2 are re-formed in the backward).
     layout: a wkv7.PackedLayout -- both token shifts and the WKV7 state restart at every sample of a row (packed_supported(x) must hold).
     carry: this layer's (att_x, ffn_x, S) of a rwkv7.TrainCarry (x is one segment of a longer row; carry_supported(x) must hold): the result
     gains the layer's next carry (att_x, ffn_x, S) as three more entries."""
     att, ffn = block.att, block.ffn
     fuse = ln_mix_supported(x) and getattr(att.args, "fused", False)
+    if (route is None) != (getattr(block, "ffn_v", None) is None):
+        raise ValueError("a Block with ffn_v needs the image mask (a RoutePlan), a Block without one takes none")
+    if carry is not None and route is not None:
+        raise NotImplementedError("a training carry together with modality routing: the carried channel-mix row would have to be re-normed per expert")
     if carry is not None:
         if layout is not None:
             raise NotImplementedError("a training carry together with packed rows")
@@ -841,10 +1016,15 @@ def _block_segment(block, x, delta, v_first, selective=False, layout=None, carry
     else:
         x, h = add_ln(x, delta, block.ln1)
         att_out, v_first = tmix_forward(att, h, v_first, recompute_state=selective) if getattr(att.args, "fused", False) else att(h, v_first)
+    if fuse and route is not None:
+        x, out = cmix_routed(block, x, att_out, route, first, selective)
+        return x, out, v_first
     if fuse:            # ln2 + the channel-mix lerp in one kernel: the LayerNorm output is never materialised
         x, (k,) = add_ln_mix(x, att_out, block.ln2, (ffn.x_k,), False, first)
         return x, cmix_from_mixed(ffn, k, recompute_relusq=selective), v_first
     x, h = add_ln(x, att_out, block.ln2)
+    if route is not None:       # no ln_mix kernels for this shape: the reference's statement, both channel mixes on every row
+        return x, torch.where(route.mask, block.ffn_v(block.ln_v(x)), ffn(h)), v_first
     return x, ffn(h), v_first
 
 
@@ -853,7 +1033,7 @@ def _block_segment_carry(block, x, delta, v_first, selective, att_x, ffn_x, S):
     return _block_segment(block, x, delta, v_first, selective, None, (att_x, ffn_x, S))
 
 
-def blocks_forward(rwkv, x, grad_cp=0, layout=None, carry=None):
+def blocks_forward(rwkv, x, grad_cp=0, layout=None, carry=None, route=None):
     """All Blocks + ln_out with the residual adds fused into the LayerNorms (same math as Block.forward chained,
     src/model.py:247-254,313-318): the residual stream is carried as (x, pending delta).
     grad_cp (the reference's memory-saving switch, src/model.py:318-319: deepspeed.checkpointing.checkpoint per block):
@@ -868,12 +1048,17 @@ def blocks_forward(rwkv, x, grad_cp=0, layout=None, carry=None):
     layout: a wkv7.PackedLayout when the rows hold several samples end to end; every mode passes it to every Block.
     carry: a rwkv7.TrainCarry when x is one segment of a longer row; every mode threads it through every Block (mode 1 checkpoints the Block
     with the carry tensors among its arguments, mode 2 lets the WKV7 state op regenerate its by-products from the carried state) and the
-    result is (hidden, the carry leaving the segment)."""
+    result is (hidden, the carry leaving the segment).
+    route: a RoutePlan when the Blocks have `ffn_v` (args.modality_ffn); every mode passes it to every Block.  Not together with a carry."""
     grad_cp = int(grad_cp) if torch.is_grad_enabled() else 0
     if grad_cp not in (0, 1, 2):
         raise ValueError(f"grad_cp = {grad_cp}: 0 (keep everything), 1 (re-compute every block, the reference's recipe) or 2 (selective recompute)")
     if carry is not None and layout is not None:
         raise NotImplementedError("a training carry together with packed rows")
+    if carry is not None and route is not None:
+        raise NotImplementedError("a training carry together with modality routing (cut rows are not routed)")
+    if route is not None:
+        route.check(x.shape[0], x.shape[1], x.device)
     x = rwkv.blocks[0].ln0(x)
     v_first = torch.empty_like(x)
     delta = None
@@ -888,9 +1073,9 @@ def blocks_forward(rwkv, x, grad_cp=0, layout=None, carry=None):
             layers.append(tuple(lc))
         elif grad_cp == 1:
             from torch.utils.checkpoint import checkpoint
-            x, delta, v_first = checkpoint(_block_segment, block, x, delta, v_first, False, layout, use_reentrant=False)
+            x, delta, v_first = checkpoint(_block_segment, block, x, delta, v_first, False, layout, None, route, use_reentrant=False)
         else:
-            x, delta, v_first = _block_segment(block, x, delta, v_first, grad_cp == 2, layout)
+            x, delta, v_first = _block_segment(block, x, delta, v_first, grad_cp == 2, layout, None, route)
     _, h = add_ln(x, delta, rwkv.ln_out)
     if carry is not None:
         from .rwkv7 import TrainCarry

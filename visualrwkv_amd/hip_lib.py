@@ -42,6 +42,10 @@ PROTOTYPES = {
     "vrwkv_ln_mix_fwd_carry_bf16": (_c_int, [_c_long, _c_int, _c_int, ctypes.c_float, _c_int] + [_c_void_p] * 12),
     "vrwkv_ln_mix_bwd_carry_bf16": (_c_int, [_c_long, _c_int, _c_int, _c_int] + [_c_void_p] * 17),
     "vrwkv_mix_bwd_ln_carry_bf16": (_c_int, [_c_long, _c_int, _c_int, _c_int] + [_c_void_p] * 15),
+    "vrwkv_ln_mix_routed_ws_floats": (_c_long, [_c_long, _c_int]),
+    "vrwkv_ln_mix_routed_fwd_bf16": (_c_int, [_c_long, _c_int, _c_int, ctypes.c_float] + [_c_void_p] * 12 + [_c_int, _c_void_p]),
+    "vrwkv_ln_mix_routed_bwd_bf16": (_c_int, [_c_long, _c_int, _c_int] + [_c_void_p] * 11 + [_c_int] + [_c_void_p] * 5),
+    "vrwkv_row_gather_bf16": (_c_int, [_c_long, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p]),
     "vrwkv_ce_fwd_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 7),
     "vrwkv_ce_bwd_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 6 + [_c_float] + [_c_void_p] * 2),
     "vrwkv_ce_bwd_rows_bf16": (_c_int, [_c_long, _c_int] + [_c_void_p] * 6 + [_c_float] + [_c_void_p] * 3),

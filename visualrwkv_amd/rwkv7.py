@@ -268,23 +268,42 @@ class RWKV_CMix_x070(nn.Module):
 
 
 class Block(nn.Module):
-    """Pre-LN residual block (src/model.py:233-254); block 0 also owns ln0."""
+    """Pre-LN residual block (src/model.py:233-254); block 0 also owns ln0.
+    args.modality_ffn = 1: the Block of VisualRWKV-v7/v7.10 (src/model.py:233-262) -- a second LayerNorm and channel mix, `ln_v` / `ffn_v`, for image
+    tokens, created in the reference's order (same state-dict keys, same draws from the random stream); forward then needs `mask` (B, T, 1) bool and
+    ends in x + where(mask, ffn_v(ln_v(x)), ffn(ln2(x)))."""
 
     def __init__(self, args, layer_id):
         super().__init__()
         self.args = args
         self.layer_id = layer_id
+        modality = bool(getattr(args, "modality_ffn", 0))
         if layer_id == 0:
             self.ln0 = nn.LayerNorm(args.n_embd)
         self.ln1 = nn.LayerNorm(args.n_embd)
         self.ln2 = nn.LayerNorm(args.n_embd)
+        if modality:
+            self.ln_v = nn.LayerNorm(args.n_embd)
         self.att = RWKV_Tmix_x070(args, layer_id)
         self.ffn = RWKV_CMix_x070(args, layer_id)
+        if modality:
+            self.ffn_v = RWKV_CMix_x070(args, layer_id)
 
-    def forward(self, x, v_first, state=None, layout=None, carry=None):
-        """carry (training across a cut): this layer's (att_x, ffn_x, S) of a TrainCarry; returns (x, v_first, the layer's next carry)."""
+    def forward(self, x, v_first, state=None, layout=None, carry=None, mask=None):
+        """carry (training across a cut): this layer's (att_x, ffn_x, S) of a TrainCarry; returns (x, v_first, the layer's next carry).
+        mask (B, T, 1) bool, required with args.modality_ffn and refused without: True = image token."""
         if self.layer_id == 0:
             x = self.ln0(x)
+        if (mask is None) != (getattr(self, "ffn_v", None) is None):
+            raise ValueError("a Block with ffn_v (args.modality_ffn) needs the image mask; a Block without one takes none")
+        if mask is not None:
+            if state is not None or carry is not None:
+                raise NotImplementedError("modality_ffn together with an inference state or a training carry: the carried channel-mix row "
+                                          "(the LayerNorm output of the last token) would have to be re-normed per expert")
+            xx, v_first = self.att(self.ln1(x), v_first, None, layout)
+            x = x + xx
+            x = x + torch.where(mask, self.ffn_v(self.ln_v(x), None, layout), self.ffn(self.ln2(x), None, layout))      # the reference's statement
+            return x, v_first
         if carry is not None:
             if state is not None or layout is not None:
                 raise NotImplementedError("a training carry together with an inference state or packed rows")
@@ -412,12 +431,21 @@ class RWKV(nn.Module):
     def unpad(self, x, num_tokens_to_pad):
         return x[:, num_tokens_to_pad:] if num_tokens_to_pad > 0 else x
 
-    def forward_features(self, x, layout=None, carry=None):
-        """Everything up to (not including) the head; returns (hidden, num_tokens_to_pad).  layout: a wkv7.PackedLayout for packed rows
+    def forward_features(self, x, layout=None, carry=None, mask=None, n_image=None):
+        """Everything up to (not including) the head; returns (hidden, num_tokens_to_pad).
+        mask (B, T, 1) bool (args.modality_ffn; True = image token): left-padded with False like x is padded (v7.10 src/model.py:350).  n_image: the
+        number of True entries when the caller counted them on the host (fused.RoutePlan then needs no device synchronisation).  layout: a wkv7.PackedLayout for packed rows
         (T is then a multiple of CHUNK_LEN by construction: no left pad).  carry: a TrainCarry when x is one segment of a longer row (T a
         multiple of CHUNK_LEN: a left pad inside a row would change it); returns (hidden, 0, the carry leaving the segment)."""
         args = self.args
+        modality = bool(getattr(args, "modality_ffn", 0))
+        if modality != (mask is not None):
+            raise ValueError("args.modality_ffn and the image mask go together: RWKV.forward(x, mask=...) with it, no mask without")
+        if mask is not None and (mask.dtype != torch.bool or tuple(mask.shape) != (x.size(0), x.size(1), 1)):
+            raise ValueError(f"mask must be ({x.size(0)}, {x.size(1)}, 1) bool, got {tuple(mask.shape)} {mask.dtype}")
         if carry is not None:
+            if mask is not None:
+                raise NotImplementedError("a training carry together with args.modality_ffn (cut rows are not routed)")
             return self._forward_features_carry(x, layout, carry)
         if layout is not None:
             layout.check(x.size(0), x.size(1), x.device)
@@ -426,12 +454,17 @@ class RWKV(nn.Module):
         rem = x.size(1) % CHUNK_LEN
         num_tokens_to_pad = CHUNK_LEN - rem if rem != 0 else 0
         x = self.pad_left(x, num_tokens_to_pad)
+        if mask is not None and num_tokens_to_pad:
+            mask = torch.cat((torch.zeros_like(mask[:, :num_tokens_to_pad]), mask), dim=1)
         if args.dropout > 0:
             x = self.drop0(x)
+        def rk():       # blocks_forward's `route` keyword, only where there is a mask: the plan is built once per batch, where a fused path takes it
+            from . import fused
+            return {"route": fused.RoutePlan(mask, n_image)} if mask is not None else {}
         if layout is not None and getattr(args, "fused", False):
             from . import fused
             if fused.packed_supported(x):
-                return fused.blocks_forward(self, x, grad_cp=int(args.grad_cp) if torch.is_grad_enabled() else 0, layout=layout), num_tokens_to_pad
+                return fused.blocks_forward(self, x, grad_cp=int(args.grad_cp) if torch.is_grad_enabled() else 0, layout=layout, **rk()), num_tokens_to_pad
         if layout is not None:
             # the unfused Blocks (masked shift in PyTorch, the WKV7 op packed on device tensors): CPU tensors, args.fused off, or the
             # two-kernel shift selected (VRWKV_LN_MIX=0), whose kernels know no sample boundaries inside a row
@@ -439,21 +472,21 @@ class RWKV(nn.Module):
             for block in self.blocks:
                 if args.grad_cp >= 1 and torch.is_grad_enabled():
                     from torch.utils.checkpoint import checkpoint
-                    x, v_first = checkpoint(block, x, v_first, None, layout, use_reentrant=False)
+                    x, v_first = checkpoint(block, x, v_first, None, layout, None, mask, use_reentrant=False)
                 else:
-                    x, v_first = block(x, v_first, None, layout)
+                    x, v_first = block(x, v_first, None, layout, None, mask)
             return self.ln_out(x), num_tokens_to_pad
         if getattr(args, "fused", False):
             from . import fused
             if fused.add_ln_supported(x):
-                return fused.blocks_forward(self, x, grad_cp=int(args.grad_cp) if torch.is_grad_enabled() else 0), num_tokens_to_pad
+                return fused.blocks_forward(self, x, grad_cp=int(args.grad_cp) if torch.is_grad_enabled() else 0, **rk()), num_tokens_to_pad
         v_first = torch.empty_like(x)
         for block in self.blocks:
             if args.grad_cp >= 1 and torch.is_grad_enabled():
                 from torch.utils.checkpoint import checkpoint
-                x, v_first = checkpoint(block, x, v_first, use_reentrant=False)
+                x, v_first = checkpoint(block, x, v_first, None, None, None, mask, use_reentrant=False)
             else:
-                x, v_first = block(x, v_first)
+                x, v_first = block(x, v_first, None, None, None, mask)
         return self.ln_out(x), num_tokens_to_pad
 
     def _forward_features_carry(self, x, layout, carry):
@@ -484,21 +517,22 @@ class RWKV(nn.Module):
             layers.append(lc)
         return self.ln_out(x), 0, TrainCarry(len(layers), layers)
 
-    def forward(self, x, hidden_only=False, layout=None, carry=None):
+    def forward(self, x, hidden_only=False, layout=None, carry=None, mask=None, n_image=None):
         """Logits (B, T, V); hidden_only: forward_features(x) instead (through the module call, so that forward pre-hooks run).
+        mask (B, T, 1) bool, n_image: see forward_features (args.modality_ffn).
         layout: a wkv7.PackedLayout when the rows hold several samples end to end.
         carry: a TrainCarry when x is one segment of a longer row; returns (logits, next carry), or forward_features' triple."""
         if carry is not None:
             if hidden_only:
-                return self.forward_features(x, layout, carry)
-            x, _, nxt = self.forward_features(x, layout, carry)
+                return self.forward_features(x, layout, carry, mask)
+            x, _, nxt = self.forward_features(x, layout, carry, mask)
             if x.is_cuda and getattr(self.args, "fused", False):
                 from . import fused
                 return fused.linear(self.head, x), nxt
             return self.head(x), nxt
         if hidden_only:
-            return self.forward_features(x, layout)
-        x, num_tokens_to_pad = self.forward_features(x, layout)
+            return self.forward_features(x, layout, None, mask, n_image)
+        x, num_tokens_to_pad = self.forward_features(x, layout, None, mask, n_image)
         if x.is_cuda and getattr(self.args, "fused", False):
             from . import fused
             x = fused.linear(self.head, x)              # input gradient in the forward GEMMs' layout
@@ -511,6 +545,9 @@ class RWKV(nn.Module):
         """Inference on embedded tokens x (B,T,C) continuing from `state` (None: empty context).  No padding is
         added: logits equal those `forward` gives for the same absolute positions of the concatenated sequence.
         Returns (logits (B,T,V) or (B,V) with last_only, state)."""
+        if getattr(self.args, "modality_ffn", 0):
+            raise NotImplementedError("forward_stateful with args.modality_ffn: the carried channel-mix row is a LayerNorm output, and the next token "
+                                      "would need it under ITS expert's LayerNorm (ln2 or ln_v); the state would have to carry the un-normed row")
         if state is None:
             state = RWKV7State(self.args, x.size(0), x.device, x.dtype, blocks=self.blocks)
         v_first = torch.empty_like(x)

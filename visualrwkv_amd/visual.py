@@ -38,13 +38,23 @@ class MLPWithContextGating(nn.Module):
         return self.o_proj(x * torch.sigmoid(self.gate(x)))
 
 
+def _embed(model, samples):
+    """(input embeddings, labels, keyword arguments of model.rwkv(...) for the image mask: none without args.modality_ffn).  A batch may carry
+    `n_image_tokens`, the count of IMAGE_TOKEN_INDEX in input_ids taken on the host (the collate): the routed path then needs no device
+    synchronisation to size its two GEMMs."""
+    res = model.preparing_embedding(samples)
+    if len(res) == 2:
+        return res[0], res[1], {}
+    return res[0], res[1], {"mask": res[2], "n_image": samples.get("n_image_tokens")}
+
+
 class VisualRWKV(nn.Module):
     def __init__(self, args):
         super().__init__()
         self.args = args
         self.rwkv = RWKV(args)
         if len(getattr(args, "load_model", "")) > 0:
-            self.rwkv.load_state_dict(torch.load(args.load_model, map_location="cpu", weights_only=True))
+            self.from_pretrained(args.load_model)
         self.vit = SamDinoSigLIPViTBackbone(getattr(args, "vision_tower_path", None),
                                             towers=getattr(args, "vision_towers", ("dino", "siglip", "sam")),
                                             default_image_size=getattr(args, "vision_image_size", 448),
@@ -56,7 +66,28 @@ class VisualRWKV(nn.Module):
             self.proj = MLPWithContextGating(self.vit.embed_dim, args.n_embd)
         self.pool = nn.AdaptiveAvgPool2d(int(args.num_token_per_image ** 0.5))
 
+    def from_pretrained(self, path):
+        """Load the language model's weights.  With args.modality_ffn the checkpoint may be a v7.00 one without `ffn_v` / `ln_v`: non-strict, as
+        v7.10 loads it (src/model.py:426-427); those keep their initialisation.  Anything else missing or unexpected is still an error."""
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if not getattr(self.args, "modality_ffn", 0):
+            self.rwkv.load_state_dict(sd)
+            return
+        res = self.rwkv.load_state_dict(sd, strict=False)
+        bad = [k for k in res.missing_keys if ".ffn_v." not in k and ".ln_v." not in k] + list(res.unexpected_keys)
+        if bad:
+            raise RuntimeError(f"from_pretrained: keys that do not match the model: {bad[:8]}{' ...' if len(bad) > 8 else ''}")
+
     # ---- freezing helpers (src/model.py:368-388)
+    def enable_pretrain_mode(self):
+        """v7.10's pre-training stage (src/model.py:438-443): the language model frozen except the image experts `ffn_v` / `ln_v` of every Block."""
+        if not getattr(self.args, "modality_ffn", 0):
+            raise ValueError("enable_pretrain_mode: the model has no ffn_v / ln_v (build it with args.modality_ffn = 1)")
+        self.rwkv.requires_grad_(False)
+        for n, p in self.rwkv.named_parameters():
+            if "ffn_v" in n or "ln_v" in n:
+                p.requires_grad_(True)
+
     def freeze_vit(self):
         self.vit.requires_grad_(False)
 
@@ -127,6 +158,16 @@ class VisualRWKV(nn.Module):
         return self.proj.pre_norm(pooled)               # ln_v is applied by the fused scatter
 
     def preparing_embedding(self, samples):
+        """(input embeddings, labels); with args.modality_ffn a third entry, the image mask (B, T, 1) bool = input_ids == IMAGE_TOKEN_INDEX
+        (v7.10 src/model.py:526)."""
+        # called unbound, and `args` probed, because tests and the golden scripts call this method on stand-in objects that carry only
+        # `rwkv`, `encode_images` and sometimes `args`
+        res = VisualRWKV._preparing_embedding(self, samples)
+        if getattr(getattr(self, "args", None), "modality_ffn", 0):
+            return (*res, (samples["input_ids"] == IMAGE_TOKEN_INDEX).unsqueeze(-1))
+        return res
+
+    def _preparing_embedding(self, samples):
         if "images" not in samples:
             return self.rwkv.emb(samples["input_ids"]), samples["labels"]
         from . import fused
@@ -174,11 +215,11 @@ class VisualRWKV(nn.Module):
         return PackedLayout(samples["seg_lens"], samples["input_ids"].shape[1], device, n_samples=samples.get("n_samples"))
 
     def forward(self, samples):
-        x, targets = self.preparing_embedding(samples)
+        x, targets, mk = _embed(self, samples)
         layout = self.packed_layout(samples, x.device)
         if layout is not None:
-            return self.rwkv(x, layout=layout), targets
-        return self.rwkv(x), targets
+            return self.rwkv(x, layout=layout, **mk), targets
+        return self.rwkv(x, **mk), targets
 
     @staticmethod
     def loss_from_logits(logits, targets, layout=None, window=None):
@@ -228,8 +269,8 @@ class VisualRWKV(nn.Module):
                 from . import fused
                 if fused.head_loss_supported(self.rwkv.head, targets):
                     plan = fused.HeadPlan(targets, 0, IGNORE_INDEX, layout)     # head + loss on the labelled rows only, per-segment weights
-                    x, _ = self.preparing_embedding(batch)
-                    h, _ = self.rwkv(x, hidden_only=True, layout=layout)
+                    x, _, mk = _embed(self, batch)
+                    h, _ = self.rwkv(x, hidden_only=True, layout=layout, **mk)
                     if fused.head_loss_supported(self.rwkv.head, targets, h):
                         return fused.head_loss(self.rwkv.head, h, plan)
                     return self.loss_from_logits(fused.linear(self.rwkv.head, h), targets, layout)
@@ -243,8 +284,8 @@ class VisualRWKV(nn.Module):
                 # head + loss as one node (backward dense on the labelled rows only); the labelled rows are counted before the forward is
                 # issued, so that the head's backward finds the count in pinned memory without waiting
                 plan = fused.HeadPlan(targets, (CHUNK_LEN - targets.shape[1] % CHUNK_LEN) % CHUNK_LEN, IGNORE_INDEX)
-                x, _ = self.preparing_embedding(batch)
-                h, num_tokens_to_pad = self.rwkv(x, hidden_only=True)
+                x, _, mk = _embed(self, batch)
+                h, num_tokens_to_pad = self.rwkv(x, hidden_only=True, **mk)
                 if num_tokens_to_pad == plan.pad and fused.head_loss_supported(self.rwkv.head, targets, h):
                     return fused.head_loss(self.rwkv.head, h, plan)
                 logits = self.rwkv.unpad(fused.linear(self.rwkv.head, h), num_tokens_to_pad)     # RWKV.forward's head
@@ -278,6 +319,9 @@ class VisualRWKV(nn.Module):
         before: no gradient crosses a cut, nothing is recomputed."""
         if batch.get("seg_lens") is not None:
             raise NotImplementedError("train_step_cut: packed rows (a batch with seg_lens) cannot be cut")
+        if getattr(self.args, "modality_ffn", 0):
+            raise NotImplementedError("train_step_cut with args.modality_ffn: cut rows are not routed (the carried channel-mix row would have to be "
+                                      "re-normed per expert)")
         targets = batch["labels"]
         B, T = targets.shape
         seg_len = int(seg_len)
@@ -345,10 +389,11 @@ class VisualRWKV(nn.Module):
         if do_sample:
             raise NotImplementedError
         samples = {"input_ids": input_ids, "images": images, "labels": torch.full_like(input_ids, IGNORE_INDEX)}
-        x, _ = self.preparing_embedding(samples)
+        x, _, mk = _embed(self, samples)
+        mk.pop("n_image", None)
         toks, lgs, prs = [], [], []
         for _ in range(max_new_tokens):
-            logits = self.rwkv(x)[:, -1, :]
+            logits = self.rwkv(x, **mk)[:, -1, :]
             nxt = torch.argmax(logits, dim=-1, keepdim=True)
             toks.append(nxt.item())
             lgs.append(logits.gather(-1, nxt).item())
@@ -356,6 +401,8 @@ class VisualRWKV(nn.Module):
             if toks[-1] == stop_token_idx:
                 break
             x = torch.cat((x, self.rwkv.emb(nxt)), dim=-2)[:, -self.args.ctx_len:, :]
+            if "mask" in mk:                                 # a generated token is text (v7.10 src/model.py:562-563)
+                mk["mask"] = torch.cat((mk["mask"], torch.zeros_like(mk["mask"][:, -1:])), dim=1)[:, -self.args.ctx_len:, :]
         return toks, lgs, prs
 
     @torch.no_grad()
@@ -368,6 +415,10 @@ class VisualRWKV(nn.Module):
         reference's per-step re-padding changes the number of pad tokens as the sequence grows."""
         if do_sample:
             raise NotImplementedError
+        if getattr(self.args, "modality_ffn", 0):
+            raise NotImplementedError("generate_stateful with args.modality_ffn: the state carries the channel-mix shift row as a LayerNorm output, and "
+                                      "with two experts the next token needs that row under its own expert's LayerNorm (ln2 or ln_v), so the carried "
+                                      "row would have to be re-normed per expert; use generate()")
         from .rwkv7 import CHUNK_LEN
         samples = {"input_ids": input_ids, "images": images, "labels": torch.full_like(input_ids, IGNORE_INDEX)}
         x, _ = self.preparing_embedding(samples)
