@@ -251,13 +251,15 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_multi_kernel(GemvArgs a) {
 }
 
 // LayerNorm fold.  The workgroup builds its job's input vectors once, cooperatively: thread t owns chunks t, t+256 of the
-// row (K <= 4096), everything it needs is loaded in one go next to nothing else, the row statistics are one LDS exchange,
-// and the bf16 inputs are parked in LDS for the four waves' row walks.  Sums are taken around the row's first element so
-// that E[d^2] - E[d]^2 does not cancel when the row has a large mean.
+// row (K <= 4096), everything it needs is loaded in one go next to nothing else,
+// and the bf16 inputs are parked in LDS for the four waves' row walks.  The row is in registers, so the statistics take two
+// passes over it (two LDS exchanges): the mean, then the variance around it, as ln_mix_prev_kernel of decode_fused.hip does.
+// One pass of sums around the row's first element (E[d^2] - E[d]^2) is exact for a large mean but cancels when that element is
+// itself the row's outlier: 1 .. 5 % of h then differ from the correctly rounded value (tests/test_decode_shapes.py).
 template <int CH, int BB>      // chunks per thread (K <= 2048 CH), batch rows compiled in: registers follow the real shape
 __global__ __launch_bounds__(GV_THREADS) void gemv_ln_kernel(GemvArgs a) {
     uint4* xin = reinterpret_cast<uint4*>(dyn_lds());                   // [B][K/8] packed bf16 inputs
-    __shared__ float red[4][BB][2];
+    __shared__ float red[2][4][BB];                                     // [pass][wave][batch row]
     const GemvJob job = a.job[find_job(a)];
     const int K = job.K, B = a.B, kchunks = K / 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -266,7 +268,6 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_ln_kernel(GemvArgs a) {
     load_batch(job, row0, lane, kchunks, first);         // the weight stream starts before the prologue's round trip
     const uint4 zero = make_uint4(0, 0, 0, 0);
     uint4 xr[CH][BB], pr[CH][BB], lwr[CH], lbr[CH], mur[CH];
-    float x0[BB];
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
         const int ch = threadIdx.x + i * GV_THREADS;
@@ -282,22 +283,39 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_ln_kernel(GemvArgs a) {
         }
     }
 #pragma unroll
-    for (int b = 0; b < BB; ++b) x0[b] = b < B ? bf16_to_f32(job.x[(size_t)b * K]) : 0.f;
-#pragma unroll
     for (int b = 0; b < BB; ++b) {
         if (b < B) {
-            float s = 0.f, s2 = 0.f;
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < CH; ++i) {
+                float xv[8];
+                unpack8(xr[i][b], xv);                   // dead chunks hold zeros
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s += xv[e];
+            }
+            s = group_sum<6>(s);
+            if (lane == 0) red[0][wave][b] = s;
+        }
+    }
+    __syncthreads();
+    float mean[BB];
+#pragma unroll
+    for (int b = 0; b < BB; ++b) {
+        mean[b] = 0.f;
+        if (b < B) {
+            mean[b] = (red[0][0][b] + red[0][1][b] + red[0][2][b] + red[0][3][b]) / (float)K;
+            float s2 = 0.f;
 #pragma unroll
             for (int i = 0; i < CH; ++i) {
                 if (threadIdx.x + i * GV_THREADS < kchunks) {
                     float xv[8];
                     unpack8(xr[i][b], xv);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { const float d = xv[e] - x0[b]; s += d; s2 = fmaf(d, d, s2); }
+                    for (int e = 0; e < 8; ++e) { const float d = xv[e] - mean[b]; s2 = fmaf(d, d, s2); }
                 }
             }
-            s = group_sum<6>(s); s2 = group_sum<6>(s2);
-            if (lane == 0) { red[wave][b][0] = s; red[wave][b][1] = s2; }
+            s2 = group_sum<6>(s2);
+            if (lane == 0) red[1][wave][b] = s2;
         }
     }
     __syncthreads();
@@ -305,10 +323,8 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_ln_kernel(GemvArgs a) {
 #pragma unroll
     for (int b = 0; b < BB; ++b) {
         if (b < B) {
-            const float s = red[0][b][0] + red[1][b][0] + red[2][b][0] + red[3][b][0];
-            const float s2 = red[0][b][1] + red[1][b][1] + red[2][b][1] + red[3][b][1];
-            const float m = s / (float)K, mean = x0[b] + m;
-            const float rstd = 1.f / sqrtf(fmaxf(s2 / (float)K - m * m, 0.f) + a.ln.eps);
+            const float s2 = red[1][0][b] + red[1][1][b] + red[1][2][b] + red[1][3][b];
+            const float rstd = 1.f / sqrtf(s2 / (float)K + a.ln.eps);
 #pragma unroll
             for (int i = 0; i < CH; ++i) {
                 const int ch = threadIdx.x + i * GV_THREADS;
@@ -317,7 +333,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_ln_kernel(GemvArgs a) {
                     unpack8(xr[i][b], xv); unpack8(pr[i][b], xp); unpack8(lwr[i], lw); unpack8(lbr[i], lb); unpack8(mur[i], mu);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        h[e] = rb((xv[e] - mean) * rstd * lw[e] + lb[e]);
+                        h[e] = rb((xv[e] - mean[b]) * rstd * lw[e] + lb[e]);
                         xv[e] = fmaf(xp[e] - h[e], mu[e], h[e]);
                     }
                     xin[b * kchunks + ch] = pack8(xv);
