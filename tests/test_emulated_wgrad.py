@@ -25,11 +25,14 @@ def test_wgrad_skinny(emu_lib, M, Nw, D, S, transposed):
     assert (out.float() - want.float()).abs().max() <= 2 * want.float().abs().max() * 2 ** -8
 
 
-@pytest.mark.parametrize("M,N1,N2,S", [(32, 256, 256, 1), (96, 256, 512, 1), (160, 512, 256, 2), (224, 256, 256, 3)])
+@pytest.mark.parametrize("M,N1,N2,S", [(32, 256, 256, 1), (96, 256, 512, 1), (160, 512, 256, 2), (224, 256, 256, 3)]
+                         + [(32 * n, 256, 256, 1) for n in (4, 5, 6, 7, 8, 9, 11)])
 def test_big_weight_gradient_kernel(emu_lib, M, N1, N2, S):
     """csrc/wgrad_big.h on the host emulator: the LDS-DMA tile images (slots XOR-ed with 4 (row & 3) on the source side), the
-    transposing operand reads of v_mfma_f32_32x32x16_bf16, the three-stage ring for 1 .. 7 stages, split-K partials + reduce --
-    lane-exact index math against fp32 A^T B."""
+    transposing operand reads of v_mfma_f32_32x32x16_bf16, the three-stage ring for 1 .. 9 and 11 stages (one slice of M / 32 stages:
+    the tail alone up to 4, one steady group with tails of 2, 3, 4, two groups with tails of 2, 3 and 5), split-K partials + reduce --
+    lane-exact index math against fp32 A^T B, and with integer operands in [-8, 8], whose products and sums fp32 holds exactly in any
+    order, equal to the fp64 product rounded once at every element."""
     g = torch.Generator().manual_seed(M + N1 + S)
     A = (torch.randn(M, N1, generator=g) * 0.5).bfloat16()
     B = (torch.randn(M, N2, generator=g) * 0.5).bfloat16()
@@ -41,4 +44,11 @@ def test_big_weight_gradient_kernel(emu_lib, M, N1, N2, S):
     assert 0 < lds <= 160 * 1024
     ref = A.float().t() @ B.float()
     assert torch.equal(out.float(), ref.bfloat16().float()) or float((out.float() - ref).norm() / ref.norm()) < 2e-3
-
+    A = torch.randint(-8, 9, (M, N1), generator=g).bfloat16()
+    B = torch.randint(-8, 9, (M, N2), generator=g).bfloat16()
+    out.fill_(float("nan"))
+    part.fill_(float("nan"))
+    emu_lib.emu_wgrad_big(M, N1, N2, S, ctypes.c_void_p(A.data_ptr()), ctypes.c_void_p(B.data_ptr()), ctypes.c_void_p(part.data_ptr()),
+                          ctypes.c_void_p(out.data_ptr()))
+    want = (A.double().t() @ B.double()).float().bfloat16().float()
+    assert bool((out.float() == want).all()), f"{int((out.float() != want).sum())} elements differ from the exact product"
