@@ -458,6 +458,29 @@ int vrwkv_ln_scatter_fwd_bf16(long ntok, int C, float eps, const void* x, const 
 int vrwkv_ln_gather_bwd_bf16(long ntok, int C, const void* dout, const long* row_index, const void* x, const float* mean,
                              const float* rstd, const void* w, void* dx, float* dwb, float* ws, void* stream);
 
+/* ---- visual token compressor (VisualRWKV-v7/v7.04/src/model.py:327-374,401-412,507-553) ------------------------------------------- */
+/* The time reversal around every second Block of VisualTokenCompressor.forward (x.flip(1) / v_first.flip(1), src/model.py:359-370), with
+ * the Block's pending residual add folded in: out[b, T-1-t, :] = bf16(x[b, t, :] + delta[b, t, :]) over (B, T, C) bf16, the add in fp32
+ * and rounded once; delta == NULL: the pure flip.  C % 8 == 0.  out must not overlap x or delta (VRWKV_EINVAL).  Its own backward:
+ * d x = d delta = flip(d out) (call it on d out with delta == NULL). */
+int vrwkv_flip_add_bf16(int B, int T, int C, const void* x, const void* delta, void* out, void* stream);
+/* The compressor's tail in one pass each way: ln_out, the removal of the left pad rows (src/model.py:372-373), nn.AdaptiveAvgPool1d over
+ * tokens (compress_visual_tokens, :524-529) and the masked scatter of preparing_embedding (:544-552).  x, delta: (B, T, C) bf16, the first
+ * `pad` rows of every sample are pad rows; Lin = T - pad.
+ *   forward : xn = bf16(x + delta) (delta == NULL: xn = x, not written); xhat = (xn - mean) rstd with the statistics of the rounded xn;
+ *             out[row_index[b Lout + i]] = bf16(fma(mean of xhat over rows pad + [floor(i Lin / Lout), ceil((i+1) Lin / Lout)), w, b)),
+ *             PyTorch's window rule, the sum in fp32.  row_index: device int64, B Lout entries, distinct rows of `out`; a negative entry
+ *             drops that output; NULL: out is (B Lout, C) in order.  mean / rstd: B T fp32 each; the entries of the pad rows, and the pad
+ *             rows of xn, are not written.  With Lout == Lin and pad == 0 this is vrwkv_ln_scatter_fwd_bf16 bit for bit.
+ *   backward: g[t] = sum over the outputs i whose window holds row t of dout[row_index[b Lout + i]] / len_i (fp32; a dropped output gives
+ *             0); dx (B, T, C) bf16 = the LayerNorm backward of vrwkv_add_ln_bwd_bf16 with g for dy, exact zeros on the pad rows;
+ *             dwb (2 C fp32) = (dgamma, dbeta), written; ws: vrwkv_add_ln_ws_floats(B T, C) floats.  Deterministic, no atomics.
+ * 1 <= Lout <= Lin, C % 64 == 0, C <= 8192 (VRWKV_ESHAPE otherwise). */
+int vrwkv_ln_pool_scatter_fwd_bf16(int B, int T, int pad, int Lout, int C, float eps, const void* x, const void* delta, const void* w,
+                                   const void* b, const long* row_index, void* xn, void* out, float* mean, float* rstd, void* stream);
+int vrwkv_ln_pool_gather_bwd_bf16(int B, int T, int pad, int Lout, int C, const void* dout, const long* row_index, const void* xn,
+                                  const float* mean, const float* rstd, const void* w, void* dx, float* dwb, float* ws, void* stream);
+
 /* The same step with the clip factor formed on the device: sqnorm[0] = squared L2 norm of the (unscaled, summed over
  * ranks) gradient, grad scale = inv_world * min(1, clip / (sqrt(sqnorm) * inv_world + 1e-6)) (clip <= 0: no clipping).
  * Replaces Lightning's gradient_clip_val=1.0 host-side norm (train.py:92) without a device -> host synchronisation. */

@@ -1,5 +1,6 @@
 // Streaming (HBM-bound) kernels around the WKV7 operator: fused AdamW on a ZeRO-1 shard, squared-norm
-// reduction for gradient clipping.  16-byte accesses, grid-stride, one pass over the data.
+// reduction for gradient clipping, the time reversal (+ pending residual add) around the visual token compressor's reversed
+// Blocks.  16-byte accesses, grid-stride, one pass over the data.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
@@ -75,6 +76,25 @@ int grid_for(long nvec) {
     return (int)(b < 1 ? 1 : b > 2048 ? 2048 : b);      // <= 8 workgroups per CU, grid-stride the rest
 }
 
+// out[b, T-1-t, :] = bf16(x[b, t, :] + delta[b, t, :]) (VisualTokenCompressor.forward's x.flip(1), VisualRWKV-v7/v7.04/src/model.py:359-370, with the
+// residual add that the Block before left pending); delta == nullptr: the pure flip.  cv = C / 8 16-byte pieces per row; a row stays contiguous, so
+// reads and writes are both whole 16-byte pieces in row order.  Each piece is read once and never again here: non-temporal both ways.
+__global__ __launch_bounds__(256) void flip_add_kernel(long nvec, int T, int cv, const uint16_t* __restrict__ x, const uint16_t* __restrict__ delta,
+                                                       uint16_t* __restrict__ out) {
+    typedef uint32_t u32x4_nt __attribute__((ext_vector_type(4)));
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / cv, c = i - r * cv;
+        const long bb = r / T, t = r - bb * T;
+        u32x4_nt u = __builtin_nontemporal_load(reinterpret_cast<const u32x4_nt*>(x) + i);
+        if (delta) {
+            const u32x4_nt d = __builtin_nontemporal_load(reinterpret_cast<const u32x4_nt*>(delta) + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) u[e] = cvt_pk_bf16(bf16_lo(u[e]) + bf16_lo(d[e]), bf16_hi(u[e]) + bf16_hi(d[e]));
+        }
+        __builtin_nontemporal_store(u, reinterpret_cast<u32x4_nt*>(out) + (bb * T + (T - 1 - t)) * cv + c);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -110,6 +130,24 @@ int vrwkv_sqnorm_bf16(long n, const void* x, float* out, void* stream) {
     if (n <= 0 || !x || !out) return VRWKV_EINVAL;
     if (n % 8 != 0) return VRWKV_ESHAPE;
     hipLaunchKernelGGL(sqnorm_bf16_kernel, dim3(grid_for(n >> 3)), dim3(256), 0, (hipStream_t)stream, n, (const uint16_t*)x, out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VRWKV_OK : (int)e;
+}
+
+int vrwkv_flip_add_bf16(int B, int T, int C, const void* x, const void* delta, void* out, void* stream) {
+    if (B <= 0 || T <= 0 || !x || !out) return VRWKV_EINVAL;
+    if (C <= 0 || C % 8 != 0) return VRWKV_ESHAPE;
+    const size_t bytes = (size_t)B * T * C * 2;
+    const uintptr_t o = reinterpret_cast<uintptr_t>(out);
+    const void* const ins[2] = {x, delta};
+    for (const void* in : ins) {                         // every output row is read from another row: an overlap cannot work in place
+        const uintptr_t a = reinterpret_cast<uintptr_t>(in);
+        if (in && o < a + bytes && a < o + bytes) return VRWKV_EINVAL;
+    }
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(delta) | o) & 15u) return VRWKV_EALIGN;
+    const long nvec = (long)B * T * (C / 8);
+    hipLaunchKernelGGL(flip_add_kernel, dim3(grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, nvec, T, C / 8, (const uint16_t*)x,
+                       (const uint16_t*)delta, (uint16_t*)out);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? VRWKV_OK : (int)e;
 }

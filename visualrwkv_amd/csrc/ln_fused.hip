@@ -44,6 +44,10 @@ inline int ln_grid(long ntok, int rows = LN_ROWS_PER_WG) {
 constexpr int LN_BWD_GRID = VRWKV_LN_BWD_GRID, LN_MIX_BWD_GRID = VRWKV_LN_MIX_BWD_GRID;
 inline int ln_bwd_grid(long ntok) { return (int)(ntok < LN_BWD_GRID ? ntok : LN_BWD_GRID); }
 inline int ln_mix_bwd_grid(long ntok) { return (int)(ntok < LN_MIX_BWD_GRID ? ntok : LN_MIX_BWD_GRID); }
+// The compressor's tail: one workgroup per pooled output (a window of Lin / Lout rows, walked with the next row in flight) up to the cap, then
+// contiguous ranges of outputs
+constexpr int LN_POOL_FWD_GRID = 1024;
+inline int ln_pool_grid(long nout) { return (int)(nout < LN_POOL_FWD_GRID ? nout : LN_POOL_FWD_GRID); }
 inline int ln_ok(int C) { return C > 0 && C % 64 == 0 && C <= 8192; }
 inline int ln_threads(int C) { return (C / 8 + 63) / 64 * 64; }
 
@@ -101,6 +105,31 @@ int vrwkv_ln_gather_bwd_bf16(long ntok, int C, const void* dout, const long* row
     const int G = ln_bwd_grid(ntok);
     hipLaunchKernelGGL(add_ln_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, (const uint16_t*)dout,
                        (const uint16_t*)nullptr, (const uint16_t*)x, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws, row_index);
+    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, (hipStream_t)stream, G, 2L * C, ws, dwb);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VRWKV_OK : (int)e;
+}
+
+// The visual token compressor's tail: ln_out, unpad, AdaptiveAvgPool1d over tokens and the scatter into the placeholder rows in one pass
+// (VisualRWKV-v7/v7.04/src/model.py:372-373,524-529,544-552); see ln_pool_fwd_kernel.  The backward's ws: vrwkv_add_ln_ws_floats(B T, C).
+int vrwkv_ln_pool_scatter_fwd_bf16(int B, int T, int pad, int Lout, int C, float eps, const void* x, const void* delta, const void* w,
+                                   const void* b, const long* row_index, void* xn, void* out, float* mean, float* rstd, void* stream) {
+    if (B <= 0 || T <= 0 || pad < 0 || pad >= T || !x || !w || !b || !out || !mean || !rstd || (delta && !xn)) return VRWKV_EINVAL;
+    if (!ln_ok(C) || Lout < 1 || Lout > T - pad) return VRWKV_ESHAPE;
+    hipLaunchKernelGGL(ln_pool_fwd_kernel, dim3(ln_pool_grid((long)B * Lout)), dim3(ln_threads(C)), 0, (hipStream_t)stream, B, T, pad, Lout, C, eps,
+                       (const uint16_t*)x, (const uint16_t*)delta, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, (uint16_t*)out, mean, rstd,
+                       row_index);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VRWKV_OK : (int)e;
+}
+
+int vrwkv_ln_pool_gather_bwd_bf16(int B, int T, int pad, int Lout, int C, const void* dout, const long* row_index, const void* xn,
+                                  const float* mean, const float* rstd, const void* w, void* dx, float* dwb, float* ws, void* stream) {
+    if (B <= 0 || T <= 0 || pad < 0 || pad >= T || !dout || !xn || !mean || !rstd || !w || !dx || !dwb || !ws) return VRWKV_EINVAL;
+    if (!ln_ok(C) || Lout < 1 || Lout > T - pad) return VRWKV_ESHAPE;
+    const int G = ln_bwd_grid((long)B * T);
+    hipLaunchKernelGGL(ln_pool_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, B, T, pad, Lout, C, (const uint16_t*)dout, row_index,
+                       (const uint16_t*)xn, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws);
     hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, (hipStream_t)stream, G, 2L * C, ws, dwb);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? VRWKV_OK : (int)e;

@@ -740,6 +740,182 @@ __global__ __launch_bounds__(LB, LB <= 256 ? 2 : 1) void ln_mix_bwd_kernel(long 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// The visual token compressor's tail (VisualRWKV-v7/v7.04/src/model.py:372-373 ln_out + unpad, :524-529 AdaptiveAvgPool1d over tokens, :544-552 the
+// masked scatter): (B, T, C) rows, the first `pad` of every sample are pad rows, Lin = T - pad; output i of a sample is the mean of the NORMALISED rows
+// pad + [floor(i Lin / Lout), ceil((i+1) Lin / Lout)) -- the affine part of the LayerNorm commutes with the mean, so it is applied once per output:
+//   out[orow[b Lout + i]] = bf16(fma(sum_t xhat[t] / len_i, w, b)),  xhat = (xn - mean) rstd,  xn = bf16(x + delta)
+// With Lout <= Lin neighbouring windows share at most one row.  A workgroup walks a contiguous range of outputs in order: the shared row is the last
+// row it normalised and stays in registers; only the first window of a range may normalise a row that the workgroup before it also does.  xn, mean
+// and rstd of a row are written by the FIRST window that holds it (one writer per address).  The pad rows are never read.
+__global__ __launch_bounds__(1024) void ln_pool_fwd_kernel(int B, int T, int pad, int Lout, int C, float eps, const uint16_t* __restrict__ x,
+                                                           const uint16_t* __restrict__ delta, const uint16_t* __restrict__ w,
+                                                           const uint16_t* __restrict__ b, uint16_t* __restrict__ xn, uint16_t* __restrict__ out,
+                                                           float* __restrict__ mean, float* __restrict__ rstd, const long* __restrict__ orow) {
+    __shared__ float red[4][MAXW][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int c0 = threadIdx.x * 8;
+    const bool act = c0 < C;
+    const long nout = (long)B * Lout;
+    const long olo = nout * blockIdx.x / gridDim.x, ohi = nout * (blockIdx.x + 1) / gridDim.x;
+    if (olo >= ohi) return;
+    const int Lin = T - pad;
+    const uint4 z4 = make_uint4(0, 0, 0, 0);
+    const V8 wv = unpack8(act ? ldg(w + c0) : z4), bv = unpack8(act ? ldg(b + c0) : z4);
+    const float inv_c = 1.f / (float)C;
+    long have = -1, done = -1;                                   // the row whose loads are in flight; the row whose xhat is in `last`
+    uint4 nx = z4, nd = z4;
+    V8 last;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) last.f[e] = 0.f;
+    int par = 0;
+    int bi = (int)(olo / Lout), i = (int)(olo - (long)bi * Lout);
+    for (long o = olo; o < ohi; ++o) {
+        const int s = (int)((long)i * Lin / Lout), e1 = (int)(((long)(i + 1) * Lin + Lout - 1) / Lout);
+        const int own0 = (int)(((long)i * Lin + Lout - 1) / Lout);               // where window i-1 ends: rows below it are that window's
+        const long base = (long)bi * T + pad;
+        V8 acc;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc.f[e] = 0.f;
+        for (int t = s; t < e1; ++t) {
+            const long n = base + t;
+            if (n != done) {
+                uint4 cx, cd = z4;
+                if (have == n) { cx = nx; cd = nd; }
+                else {
+                    cx = act ? ldg(x + n * C + c0) : z4;
+                    if (act && delta) cd = ldg(delta + n * C + c0);
+                }
+                // the next row this workgroup normalises: t + 1 of this window, or of the next window of the same sample (t + 1 < Lin then)
+                if (t + 1 < e1 || (i + 1 < Lout && o + 1 < ohi)) {
+                    have = n + 1;
+                    if (act) {
+                        nx = ldg(x + (n + 1) * C + c0);
+                        if (delta) nd = ldg(delta + (n + 1) * C + c0);
+                    }
+                }
+                const bool own = t >= own0;
+                V8 v = unpack8(cx);
+                if (delta) {
+                    const V8 d = unpack8(cd);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v.f[e] += d.f[e];
+                    const uint4 r = pack8(v);
+                    if (act && own) stg(xn + n * C + c0, r);
+                    v = unpack8(r);
+                }
+                float sm[1] = {0.f};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sm[0] += v.f[e];
+                block_sum<1>(red, par, wave, lane, nw, sm);
+                const float mu = sm[0] * inv_c;
+                float q[1] = {0.f};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float d = act ? v.f[e] - mu : 0.f; q[0] = fmaf(d, d, q[0]); }
+                block_sum<1>(red, par + 1, wave, lane, nw, q);
+                par ^= 2;
+                const float rs = rsqrtf(q[0] * inv_c + eps);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) last.f[e] = (v.f[e] - mu) * rs;
+                if (own && threadIdx.x == 0) { mean[n] = mu; rstd[n] = rs; }
+                done = n;
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc.f[e] = t == s ? last.f[e] : acc.f[e] + last.f[e];
+        }
+        const float inv_len = 1.f / (float)(e1 - s);
+        V8 r;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) r.f[e] = fmaf(acc.f[e] * inv_len, wv.f[e], bv.f[e]);
+        const long dst = orow ? orow[o] : o;                     // a negative row is dropped
+        if (act && dst >= 0) stg(out + dst * C + c0, pack8(r));
+        if (++i == Lout) { i = 0; ++bi; }
+    }
+}
+
+// ... and its backward: row t of a sample collects g = sum_i dout[orow[b Lout + i]] / len_i over the one or two windows that hold it (fp32, a dropped
+// output gives 0), then add_ln_bwd_kernel's row with g for dy.  The pad rows get zeros and read nothing (their mean / rstd are unwritten).  A
+// workgroup walks a contiguous range of the B T rows; the next row's loads are issued before this row's reduction.
+__global__ __launch_bounds__(1024) void ln_pool_bwd_kernel(int B, int T, int pad, int Lout, int C, const uint16_t* __restrict__ dout,
+                                                           const long* __restrict__ orow, const uint16_t* __restrict__ xn,
+                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                           const uint16_t* __restrict__ w, uint16_t* __restrict__ dx, float* __restrict__ part) {
+    __shared__ float red[2][MAXW][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int c0 = threadIdx.x * 8;
+    const bool act = c0 < C;
+    const long ntok = (long)B * T;
+    const long lo = ntok * blockIdx.x / gridDim.x, hi = ntok * (blockIdx.x + 1) / gridDim.x;
+    const int Lin = T - pad;
+    const uint4 z4 = make_uint4(0, 0, 0, 0);
+    const V8 wv = unpack8(act ? ldg(w + c0) : z4);
+    const float inv_c = 1.f / (float)C;
+    V8 gw, gb;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { gw.f[e] = 0.f; gb.f[e] = 0.f; }
+    struct Row { uint4 x, d0, d1; float s0, s1, mu, rs; };
+    // everything row (bb, t >= pad) needs: its xn and statistics, the gradient rows of its windows and their 1 / len
+    auto fetch = [&](long n, int bb, int t) {
+        Row r{z4, z4, z4, 0.f, 0.f, 0.f, 0.f};
+        const int tt = t - pad;
+        const int i0 = (int)((long)tt * Lout / Lin), i1 = (int)(((long)(tt + 1) * Lout + Lin - 1) / Lin) - 1;
+        auto len = [&](int i) { return (int)(((long)(i + 1) * Lin + Lout - 1) / Lout) - (int)((long)i * Lin / Lout); };
+        const long o0 = (long)bb * Lout + i0;
+        const long r0 = orow ? orow[o0] : o0;
+        if (act && r0 >= 0) r.d0 = ldg(dout + r0 * C + c0);
+        r.s0 = 1.f / (float)len(i0);
+        if (i1 > i0) {
+            const long r1 = orow ? orow[o0 + 1] : o0 + 1;
+            if (act && r1 >= 0) r.d1 = ldg(dout + r1 * C + c0);
+            r.s1 = 1.f / (float)len(i0 + 1);
+        }
+        if (act) r.x = ldg(xn + n * C + c0);
+        r.mu = mean[n]; r.rs = rstd[n];
+        return r;
+    };
+    int bi = (int)(lo / T), t = (int)(lo - (long)bi * T);
+    Row nxt{z4, z4, z4, 0.f, 0.f, 0.f, 0.f};
+    if (lo < hi && t >= pad) nxt = fetch(lo, bi, t);
+    int slot = 0;
+    for (long n = lo; n < hi; ++n) {
+        const Row cur = nxt;
+        const bool real = t >= pad;
+        if (++t == T) { t = 0; ++bi; }
+        if (n + 1 < hi && t >= pad) nxt = fetch(n + 1, bi, t);
+        if (!real) {                                             // workgroup-uniform
+            if (act) stg(dx + n * C + c0, z4);
+            continue;
+        }
+        const V8 a0 = unpack8(cur.d0), a1 = unpack8(cur.d1), xv = unpack8(cur.x);
+        V8 xh, g;
+        float s[2] = {0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float d = fmaf(a1.f[e], cur.s1, a0.f[e] * cur.s0);
+            xh.f[e] = act ? (xv.f[e] - cur.mu) * cur.rs : 0.f;
+            g.f[e] = d * wv.f[e];
+            s[0] += g.f[e];
+            s[1] = fmaf(g.f[e], xh.f[e], s[1]);
+            gw.f[e] = fmaf(d, xh.f[e], gw.f[e]);
+            gb.f[e] += d;
+        }
+        block_sum<2>(red, slot, wave, lane, nw, s);
+        slot ^= 1;
+        const float c1 = s[0] * inv_c, c2 = s[1] * inv_c;
+        V8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o.f[e] = fmaf(cur.rs, g.f[e] - c1 - xh.f[e] * c2, 0.f);
+        if (act) stg(dx + n * C + c0, pack8(o));
+    }
+    if (act) {
+        float* dst = part + (size_t)blockIdx.x * 2 * C + c0;
+        *reinterpret_cast<float4*>(dst) = make_float4(gw.f[0], gw.f[1], gw.f[2], gw.f[3]);
+        *reinterpret_cast<float4*>(dst + 4) = make_float4(gw.f[4], gw.f[5], gw.f[6], gw.f[7]);
+        *reinterpret_cast<float4*>(dst + C) = make_float4(gb.f[0], gb.f[1], gb.f[2], gb.f[3]);
+        *reinterpret_cast<float4*>(dst + C + 4) = make_float4(gb.f[4], gb.f[5], gb.f[6], gb.f[7]);
+    }
+}
+
 // dst[i] = src[idx[i]] on rows of C bf16 (cv = C / 8 16-byte pieces per row; idx int32, or int64 with IDX64): the routed channel mix's way back to
 // token order, and with the inverse index that step's backward
 template <bool IDX64>

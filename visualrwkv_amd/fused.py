@@ -1667,6 +1667,184 @@ def ln_scatter(embeds2d, y2d, ln, row_index):
 
 
 # ------------------------------------------------------------------------------------------------
+# Visual token compressor (VisualRWKV-v7/v7.04 src/model.py:327-374,516-529): time reversal around every second Block, and the tail
+# ln_out + unpad + AdaptiveAvgPool1d over tokens + scatter (csrc/fused_ops.hip: flip_add; csrc/ln_fused.hip: ln_pool_*)
+# ------------------------------------------------------------------------------------------------
+class _FlipAdd(torch.autograd.Function):
+    """out[b, T-1-t] = x[b, t] + delta[b, t] (delta may be None: the pure flip).  Its own backward: d x = d delta = flip(d out), one tensor."""
+
+    @staticmethod
+    def forward(ctx, x, delta):
+        B, T, C = x.shape
+        x = x.contiguous()
+        delta = delta.contiguous() if delta is not None else None
+        _chk(x, delta)
+        if delta is not None and delta.shape != x.shape:
+            raise ValueError("flip_add: x and delta must have the same shape")
+        out = torch.empty_like(x)
+        hip_lib.check(hip_lib.load().vrwkv_flip_add_bf16(B, T, C, x.data_ptr(), _p(delta), out.data_ptr(), _stream(x)), "vrwkv_flip_add_bf16")
+        ctx.has_delta = delta is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, T, C = dout.shape
+        dout = dout.contiguous()
+        _chk(dout)
+        dx = torch.empty_like(dout)
+        hip_lib.check(hip_lib.load().vrwkv_flip_add_bf16(B, T, C, dout.data_ptr(), 0, dx.data_ptr(), _stream(dout)), "vrwkv_flip_add_bf16")
+        return dx, (dx if ctx.has_delta else None)
+
+
+def flip_add(x, delta=None):
+    """(x + delta).flip(1) of (B, T, C) bf16 in one pass; delta may be None."""
+    return _FlipAdd.apply(x, delta)
+
+
+class _LnPoolScatter(torch.autograd.Function):
+    """The compressor's tail: LayerNorm(x + delta) of (B, T, C), the first `pad` rows of every sample dropped, AdaptiveAvgPool1d(Lout) over the
+    remaining tokens, output b * Lout + i written to row row_index[b * Lout + i] of `embeds` (rows, C), which is modified in place and returned; a
+    negative row drops that output.  embeds = None: a new dense (B * Lout, C) tensor in order (row_index must be None too)."""
+
+    @staticmethod
+    def forward(ctx, embeds, x, delta, w, b, row_index, pad, Lout, eps):
+        B, T, C = x.shape
+        x = x.contiguous()
+        delta = delta.contiguous() if delta is not None else None
+        wc, bc = w.contiguous(), b.contiguous()
+        _chk(embeds, x, delta, wc, bc)
+        if (embeds is None) != (row_index is None):
+            raise ValueError("ln_pool_scatter: `embeds` and `row_index` go together")
+        if row_index is not None and (row_index.dtype != torch.int64 or row_index.numel() != B * Lout or row_index.device != x.device
+                                      or not row_index.is_contiguous()):
+            raise ValueError(f"ln_pool_scatter: row_index must hold {B * Lout} contiguous int64 rows on {x.device}")
+        if embeds is not None and (embeds.dim() != 2 or embeds.shape[1] != C or not embeds.is_contiguous()):
+            raise ValueError("ln_pool_scatter: embeds must be a contiguous (rows, C) tensor")
+        out = embeds if embeds is not None else torch.empty(B * Lout, C, dtype=x.dtype, device=x.device)
+        xn = torch.empty_like(x) if delta is not None else x
+        mean = torch.empty(B * T, dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        rc = hip_lib.load().vrwkv_ln_pool_scatter_fwd_bf16(B, T, int(pad), int(Lout), C, float(eps), x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
+                                                           _p(row_index), xn.data_ptr() if delta is not None else 0, out.data_ptr(), mean.data_ptr(),
+                                                           rstd.data_ptr(), _stream(x))
+        hip_lib.check(rc, "vrwkv_ln_pool_scatter_fwd_bf16")
+        if embeds is not None:
+            ctx.mark_dirty(embeds)
+        ctx.save_for_backward(xn, mean, rstd, wc, row_index)
+        ctx.geom = (int(pad), int(Lout))
+        ctx.has_delta, ctx.scatter = delta is not None, embeds is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xn, mean, rstd, wc, row_index = ctx.saved_tensors
+        B, T, C = xn.shape
+        pad, Lout = ctx.geom
+        dout = dout.contiguous()
+        _chk(dout)
+        lib = hip_lib.load()
+        dx = torch.empty_like(xn)
+        dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
+        ws = torch.empty(lib.vrwkv_add_ln_ws_floats(B * T, C), dtype=torch.float32, device=xn.device)
+        rc = lib.vrwkv_ln_pool_gather_bwd_bf16(B, T, pad, Lout, C, dout.data_ptr(), _p(row_index), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                               wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
+        hip_lib.check(rc, "vrwkv_ln_pool_gather_bwd_bf16")
+        d_emb = None
+        if ctx.scatter and ctx.needs_input_grad[0]:    # as _LnScatter: rows that were overwritten do not reach the embedding
+            R = dout.shape[0]
+            d_emb = torch.empty(R + 1, C, dtype=dout.dtype, device=dout.device)
+            d_emb[:R] = dout
+            d_emb.index_fill_(0, torch.where(row_index < 0, R, row_index), 0)
+            d_emb = d_emb[:R]
+        return d_emb, dx, (dx if ctx.has_delta else None), dwb[0].to(wc.dtype), dwb[1].to(wc.dtype), None, None, None, None
+
+
+def ln_pool_scatter(x, delta, ln, pad, Lout, embeds2d=None, row_index=None):
+    """See `_LnPoolScatter`; returns embeds2d (modified in place), or the dense (B * Lout, C) result when it is None."""
+    return _LnPoolScatter.apply(embeds2d, x, delta, ln.weight, ln.bias, row_index, pad, Lout, ln.eps)
+
+
+VTC_TAIL = os.environ.get("VRWKV_VTC_TAIL", "1") != "0"           # A/B switch: 0 = add_ln, torch's adaptive_avg_pool1d and index_copy for the tail
+
+
+def vtc_supported(vtc, x):
+    """May the compressor take vtc_forward?  bf16 on the GPU with args.fused, rows the LayerNorm kernels accept."""
+    return (bool(getattr(vtc.args, "fused", False)) and add_ln_supported(x) and x.dim() == 3 and vtc.ln_out.weight.dtype == torch.bfloat16
+            and len(vtc.blocks) > 0)
+
+
+def vtc_pad(x):
+    """VisualTokenCompressor.pad_left (src/model.py:334-342, 353-356): ZERO rows on the left up to a multiple of 16 tokens.  Returns (x, pad)."""
+    pad = (-x.shape[1]) % 16
+    if pad:
+        x = torch.cat((torch.zeros(x.shape[0], pad, x.shape[2], dtype=x.dtype, device=x.device), x), dim=1)
+    return x, pad
+
+
+def vtc_forward(vtc, x, grad_cp=0, layout=None):
+    """The Blocks of a rwkv7.VisualTokenCompressor on the already padded (B, T, C) rows (VisualTokenCompressor.forward, src/model.py:358-370), through
+    _block_segment on the (x, pending delta) residual stream: every second Block runs on the time-reversed rows.  The flip into a reversed Block takes
+    the pending residual add with it (flip_add), and so does the flip out of it, so neither add is paid twice.  v_first is written by Block 0 alone
+    and only read after it: it is flipped once, every reversed Block reads that copy, and its gradient comes back through that one flip.
+    The pad rows are ordinary rows, as in the reference: after a reversed Block they hold what the recurrence left there.
+    grad_cp as in blocks_forward; mode 1 checkpoints the Block, the flips stay outside.  Returns (x, delta): ln_out is the caller's (ln_pool_scatter,
+    or add_ln for the 'step' reduction)."""
+    if layout is not None:
+        raise NotImplementedError("packed rows inside the compressor: the flips reverse whole rows (rwkv7.VisualTokenCompressor.forward)")
+    grad_cp = int(grad_cp) if torch.is_grad_enabled() else 0
+    if grad_cp not in (0, 1, 2):
+        raise ValueError(f"grad_cp = {grad_cp}: 0, 1 or 2 (see blocks_forward)")
+    if x.shape[1] % 16 != 0:
+        raise ValueError(f"vtc_forward: T = {x.shape[1]} must be a multiple of 16 (vtc_pad)")
+    x = vtc.blocks[0].ln0(x)
+    v_fwd, v_rev = torch.empty_like(x), None
+    delta = None
+    for i, block in enumerate(vtc.blocks):
+        rev = i % 2 == 1
+        if rev:
+            x, delta = flip_add(x, delta), None
+            if v_rev is None:
+                v_rev = flip_add(v_fwd)
+        v_in = v_rev if rev else v_fwd
+        if grad_cp == 1:
+            from torch.utils.checkpoint import checkpoint
+            x, delta, v_out = checkpoint(_block_segment, block, x, delta, v_in, False, None, None, None, use_reentrant=False)
+        else:
+            x, delta, v_out = _block_segment(block, x, delta, v_in, grad_cp == 2)
+        if i > 0 and (v_out.data_ptr() != v_in.data_ptr() or v_out.shape != v_in.shape):
+            raise AssertionError(f"vtc_forward: Block {i} returned another v_first than it was given; the flipped copy cannot be reused")
+        if rev:
+            v_rev = v_out
+            x, delta = flip_add(x, delta), None
+        else:
+            v_fwd = v_out
+    return x, delta
+
+
+def vtc_compress(vtc, feats, Lout, reduction="pool", embeds2d=None, row_index=None, grad_cp=0):
+    """compress_visual_tokens on the fused path (src/model.py:516-529): feats (B, N L, C) -> pad -> Blocks -> ln_out -> unpad -> reduction.
+    'pool': AdaptiveAvgPool1d(Lout) over tokens, written into rows `row_index` of embeds2d (returned), or returned as (B, Lout, C) when embeds2d is None.
+    'step': every (N L // Lout)-th token, as the reference's slice; (B, ceil(N L / step), C)."""
+    B, Lin, C = feats.shape
+    x, pad = vtc_pad(feats)
+    x, delta = vtc_forward(vtc, x, grad_cp)
+    if reduction == "step":
+        _, h = add_ln(x, delta, vtc.ln_out)
+        return h[:, pad:][:, ::Lin // Lout]
+    if reduction != "pool":
+        raise ValueError(f"reduction = {reduction!r}: 'pool' or 'step'")
+    if not VTC_TAIL:                                # the composite of what existed before the tail kernels
+        _, h = add_ln(x, delta, vtc.ln_out)
+        pooled = F.adaptive_avg_pool1d(h[:, pad:].permute(0, 2, 1), Lout).permute(0, 2, 1)
+        if embeds2d is None:
+            return pooled
+        keep = row_index >= 0
+        return embeds2d.index_copy(0, row_index[keep], pooled.reshape(B * Lout, C)[keep])
+    out = ln_pool_scatter(x, delta, vtc.ln_out, pad, Lout, embeds2d, row_index)
+    return out if embeds2d is not None else out.view(B, Lout, C)
+
+
+# ------------------------------------------------------------------------------------------------
 # Patch embedding of the frozen towers (csrc/patch_embed_kernels.h)
 # ------------------------------------------------------------------------------------------------
 _PATCH_SIZES = (14, 16)

@@ -403,6 +403,70 @@ class RWKV7State:
         return (outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)).view(B, T, HC)
 
 
+class VisualTokenCompressor(nn.Module):
+    """The visual token compressor of VisualRWKV-v7/v7.03 and v7.04 (src/model.py:327-374): args.n_vtc_layer plain v7.00 Blocks (Block 0 owns ln0)
+    over all image tokens of a sample, every second Block on the time-reversed sequence, then its own ln_out.  Same sub-module names, so the
+    reference's state-dict keys `blocks.{i}.*`, `ln_out.*` in its order.  This is the eager statement (`.flip(1)`); the GPU path is
+    fused.vtc_forward with the tail kernels.  The Blocks are built from a copy of args without state_tune / modality_ffn: the compressor has
+    neither tuned states nor image experts."""
+
+    def __init__(self, args):
+        super().__init__()
+        import copy
+        self.args = args
+        bargs = copy.copy(args)
+        bargs.state_tune = 0
+        bargs.modality_ffn = 0
+        self.blocks = nn.ModuleList([Block(bargs, i) for i in range(args.n_vtc_layer)])
+        self.ln_out = nn.LayerNorm(args.n_embd)
+
+    def pad_left(self, x, num_tokens_to_pad):
+        """ZERO rows on the left (src/model.py:334-342) -- not the EOS embedding that RWKV.pad_left uses."""
+        if num_tokens_to_pad != 0:
+            x = torch.cat((torch.zeros(x.size(0), num_tokens_to_pad, x.size(2), dtype=x.dtype, device=x.device), x), dim=1)
+        return x
+
+    def unpad(self, x, num_tokens_to_pad):
+        return x[:, num_tokens_to_pad:] if num_tokens_to_pad > 0 else x
+
+    def forward(self, x, layout=None, tail=None):
+        """x (B, L, C) -> (B, L, C).  tail = (Lout, reduction[, embeds2d, row_index]): also compress_visual_tokens' reduction to Lout tokens ('pool' /
+        'step', src/model.py:521-529); on the fused path 'pool' may write straight into rows `row_index` of the (rows, C) token embeddings
+        (fused.vtc_compress), which are then returned.  Calling the module (rather than fused.vtc_forward) lets forward pre-hooks run."""
+        if layout is not None:
+            raise NotImplementedError("packed rows inside the compressor: a reversed Block would run every sample of the row backwards into its "
+                                      "neighbour; the compressor takes one sample per row")
+        if tail is not None:
+            from . import fused
+            Lout, reduction, *scatter = tail
+            if fused.vtc_supported(self, x):
+                return fused.vtc_compress(self, x, Lout, reduction, *scatter, grad_cp=getattr(self.args, "grad_cp", 0))
+            if scatter:
+                raise NotImplementedError("the scatter into the token embeddings is the fused path's (bf16 on the GPU, args.fused)")
+            h = self.forward(x)
+            if reduction == "step":
+                return h[:, ::x.size(1) // Lout, :]
+            if reduction != "pool":
+                raise ValueError(f"reduction = {reduction!r}: 'pool' or 'step'")
+            return F.adaptive_avg_pool1d(h.permute(0, 2, 1), Lout).permute(0, 2, 1)
+        rem = x.size(1) % CHUNK_LEN
+        num_tokens_to_pad = CHUNK_LEN - rem if rem != 0 else 0
+        x = self.pad_left(x, num_tokens_to_pad)
+        v_first = torch.empty_like(x)
+        for i, block in enumerate(self.blocks):
+            reverse = i % 2 == 1
+            if reverse:             # the pad rows are ordinary rows: after a reversed Block they hold values that the next Block reads
+                x, v_first = x.flip(1), v_first.flip(1)
+            if getattr(self.args, "grad_cp", 0) >= 1 and torch.is_grad_enabled():
+                from torch.utils.checkpoint import checkpoint
+                x, v_first = checkpoint(block, x, v_first, use_reentrant=False)
+            else:
+                x, v_first = block(x, v_first)
+            if reverse:
+                x, v_first = x.flip(1), v_first.flip(1)
+        return self.unpad(self.ln_out(x), num_tokens_to_pad)
+
+
 class RWKV(nn.Module):
     """Embedding -> n_layer Blocks -> ln_out -> head, on already-embedded inputs (src/model.py:273-325).
 

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 from torch.nn import functional as F
 
-from .rwkv7 import IGNORE_INDEX, IMAGE_TOKEN_INDEX, L2Wrap, L2WrapWindow, RWKV, TrainCarry
+from .rwkv7 import IGNORE_INDEX, IMAGE_TOKEN_INDEX, L2Wrap, L2WrapWindow, RWKV, TrainCarry, VisualTokenCompressor
 from .vit import SamDinoSigLIPViTBackbone
 
 
@@ -65,6 +65,27 @@ class VisualRWKV(nn.Module):
         else:
             self.proj = MLPWithContextGating(self.vit.embed_dim, args.n_embd)
         self.pool = nn.AdaptiveAvgPool2d(int(args.num_token_per_image ** 0.5))
+        if int(getattr(args, "n_vtc_layer", 0) or 0) > 0:
+            # v7.03 / v7.04 (src/model.py:401-403): the trainable compressor after the projector takes the place of the fixed 2-D pool before it
+            if getattr(args, "modality_ffn", 0):
+                raise NotImplementedError("args.n_vtc_layer together with args.modality_ffn: the compressor belongs to v7.03 / v7.04, the image "
+                                          "experts to v7.10; no reference model has both")
+            if getattr(args, "proj_type", "mlp") == "linear":
+                raise NotImplementedError("args.n_vtc_layer with proj_type = 'linear': the compressor follows MLPWithContextGating's ln_v")
+            self.vtc = VisualTokenCompressor(args)
+
+    @property
+    def has_vtc(self):
+        return getattr(self, "vtc", None) is not None
+
+    def init_vtc_weights(self):
+        """Start the compressor from the language model (src/model.py:406-412): ln_out and the first n_vtc_layer Blocks, copied.  Call it after the
+        language model's weights are loaded."""
+        if not self.has_vtc:
+            raise ValueError("init_vtc_weights: the model has no compressor (build it with args.n_vtc_layer > 0)")
+        self.vtc.ln_out.load_state_dict(self.rwkv.ln_out.state_dict())
+        for i in range(self.args.n_vtc_layer):
+            self.vtc.blocks[i].load_state_dict(self.rwkv.blocks[i].state_dict())
 
     def from_pretrained(self, path):
         """Load the language model's weights.  With args.modality_ffn the checkpoint may be a v7.00 one without `ffn_v` / `ln_v`: non-strict, as
@@ -152,10 +173,29 @@ class VisualRWKV(nn.Module):
             for i in range(0, n, minibatch_size):
                 feats.append(self.vit({k: images[k][i:i + minibatch_size] for k in keys}))
         image_features = feats[0] if len(feats) == 1 else torch.cat(feats, dim=0)
-        pooled = self.adaptive_pooling(image_features.detach())
+        # with a compressor every token of every image goes through the projector (v7.04 src/model.py:507-514: no 2-D pool)
+        pooled = image_features.detach() if getattr(self, "vtc", None) is not None else self.adaptive_pooling(image_features.detach())
         if normed:
             return self.proj(pooled)
         return self.proj.pre_norm(pooled)               # ln_v is applied by the fused scatter
+
+    def _images_per_sample(self, n_images, B):
+        if B <= 0 or n_images % B != 0:
+            raise ValueError(f"the compressor runs over all image tokens of a sample: {n_images} images do not divide among {B} samples")
+        return n_images // B
+
+    def compress_visual_tokens(self, image_features, reduction="pool"):
+        """(B, N, L, D) projected image tokens -> the compressor over the N L tokens of each sample -> (B, N * num_token_per_image, D)
+        (v7.04 src/model.py:516-529).  'pool': AdaptiveAvgPool1d over tokens; 'step': every (L // num_token_per_image)-th token."""
+        if getattr(self, "vtc", None) is None:
+            raise ValueError("compress_visual_tokens: the model has no compressor (build it with args.n_vtc_layer > 0)")
+        if reduction not in ("pool", "step"):
+            raise ValueError(f"reduction = {reduction!r}: 'pool' or 'step'")
+        B, N, L, D = image_features.shape
+        ntpi = int(self.args.num_token_per_image)
+        if ntpi > L:
+            raise ValueError(f"num_token_per_image = {ntpi} is more than the {L} tokens of an image: the compressor only reduces")
+        return self.vtc(image_features.reshape(B, N * L, D), tail=(ntpi * N, reduction))
 
     def preparing_embedding(self, samples):
         """(input embeddings, labels); with args.modality_ffn a third entry, the image mask (B, T, 1) bool = input_ids == IMAGE_TOKEN_INDEX
@@ -175,6 +215,43 @@ class VisualRWKV(nn.Module):
         B, Ln = ids.shape
         D = self.rwkv.emb.weight.shape[1]
         selected = ids.reshape(B * Ln) == IMAGE_TOKEN_INDEX
+        vtc = getattr(self, "vtc", None)
+        if (vtc is not None and getattr(self.args, "fused", False) and ids.is_cuda and self.rwkv.emb.weight.dtype == torch.bfloat16
+                and not getattr(self.args, "check_image_tokens", True) and self.proj.ln_v.weight.dtype == torch.bfloat16
+                and vtc.ln_out.weight.dtype == torch.bfloat16 and D % 64 == 0 and D <= 8192):
+            # GPU path with a compressor: ln_v (one kernel: it feeds the compressor and cannot move into the scatter), the Blocks with their flips,
+            # then ln_out + unpad + pool + scatter into the placeholder rows in one pass.  Same row list and surplus rule as below.
+            pre = self.encode_images(samples["images"], normed=False)
+            N = self._images_per_sample(pre.shape[0], B)
+            ntpi = int(self.args.num_token_per_image)
+            if ntpi > pre.shape[1]:
+                raise ValueError(f"num_token_per_image = {ntpi} is more than the {pre.shape[1]} tokens of an image: the compressor only reduces")
+            _, feats = fused.add_ln(pre.reshape(B, N * pre.shape[1], D), None, self.proj.ln_v)
+            input_embeds = self.rwkv.emb(ids).view(B * Ln, D)
+            n_feat = B * N * ntpi
+            rows = torch.argsort(~selected, stable=True)
+            if n_feat > B * Ln:                              # more features than tokens at all: the surplus has no row
+                rows = torch.cat((rows, rows.new_zeros(n_feat - B * Ln)))
+                ok = torch.arange(n_feat, device=rows.device) < B * Ln
+                rows = torch.where(ok & selected[rows], rows, torch.full_like(rows, -1))
+            else:
+                rows = rows[:n_feat]
+                rows = torch.where(selected[rows], rows, torch.full_like(rows, -1))
+            input_embeds = vtc(feats, tail=(N * ntpi, "pool", input_embeds, rows.contiguous()))
+            return input_embeds.view(B, Ln, D), samples["labels"]
+        if vtc is not None:
+            input_embeds = self.rwkv.emb(ids).view(B * Ln, D)
+            image_features = self.encode_images(samples["images"])
+            N = self._images_per_sample(image_features.shape[0], B)
+            image_features = self.compress_visual_tokens(image_features.view(B, N, *image_features.shape[1:]))
+            image_features = image_features.reshape(-1, image_features.shape[-1])
+            n_sel = int(selected.sum())
+            if n_sel != image_features.shape[0]:
+                n_feat = image_features.shape[0]
+                image_features = image_features[:n_sel]      # the reference truncates and warns (v7.04 src/model.py:546-550)
+                warnings.warn(f"image tokens: {n_sel}, but image features: {n_feat}")
+            input_embeds = input_embeds.masked_scatter(selected[:, None], image_features.to(input_embeds.dtype))
+            return input_embeds.view(B, Ln, D), samples["labels"]
         if (getattr(self.args, "fused", False) and isinstance(getattr(self, "proj", None), MLPWithContextGating) and ids.is_cuda
                 and self.rwkv.emb.weight.dtype == torch.bfloat16 and not getattr(self.args, "check_image_tokens", True)
                 and self.proj.ln_v.weight.dtype == torch.bfloat16 and D % 64 == 0):
@@ -319,6 +396,8 @@ class VisualRWKV(nn.Module):
         before: no gradient crosses a cut, nothing is recomputed."""
         if batch.get("seg_lens") is not None:
             raise NotImplementedError("train_step_cut: packed rows (a batch with seg_lens) cannot be cut")
+        if getattr(self, "vtc", None) is not None:
+            raise NotImplementedError("train_step_cut with args.n_vtc_layer is not built: the compressor's rows are not cut; use training_step")
         if getattr(self.args, "modality_ffn", 0):
             raise NotImplementedError("train_step_cut with args.modality_ffn: cut rows are not routed (the carried channel-mix row would have to be "
                                       "re-normed per expert)")
