@@ -50,6 +50,113 @@ constexpr int LN_POOL_FWD_GRID = 1024;
 inline int ln_pool_grid(long nout) { return (int)(nout < LN_POOL_FWD_GRID ? nout : LN_POOL_FWD_GRID); }
 inline int ln_ok(int C) { return C > 0 && C % 64 == 0 && C <= 8192; }
 inline int ln_threads(int C) { return (C / 8 + 63) / 64 * 64; }
+inline void colsum(int G, long width, const float* part, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(width / 16)), dim3(256), 0, st, G, width, part, out);
+}
+inline int done() { hipError_t e = hipGetLastError(); return e == hipSuccess ? VRWKV_OK : (int)e; }
+
+// The ln_mix kernels' host side: one description of a launch each way, the variants (the kernels' PK / CARRY / ROUTED flags) its optional
+// fields -- left NULL they select the plain kernel (route: the kernels' own LmRoute).  The vrwkv_ln_mix_* entries below fill one and call
+// ln_mix_fwd / ln_mix_bwd, which validate, pick the instantiation and, in the backward, sum the per-workgroup partial rows.
+inline bool route_ok(const LmRoute& r) { return r.w1 && r.b1 && r.mu1 && r.sel && r.pos; }
+struct LnMixFwd {
+    long ntok; int T, C; float eps; int M;
+    const void *x, *delta, *w, *b; const void* const* mu;
+    void* xn; void* const* out; float *mean, *rstd;
+    void* stream;
+    const unsigned char* first = nullptr;                       // PK
+    const void* y_prev = nullptr; void* y_last = nullptr;       // CARRY
+    const LmRoute* route = nullptr;                             // ROUTED (M = 1; mu[0], out[0]: expert 0's lerp, the routed tensor)
+    bool carry() const { return y_prev || y_last; }
+};
+struct LnMixBwd {                                               // M = 1 only, see vrwkv_ln_mix_bwd_bf16
+    long ntok; int T, C, M;
+    const void* xn; const float *mean, *rstd; const void *w, *b; const void* const* mu;
+    const void* const* dout; const void* dout3_second; const void* dres;
+    void* dx; float *dwb, *dmu, *ws;
+    void* stream;
+    const unsigned char* first = nullptr;                                                       // PK
+    const void* y_prev = nullptr; const float* dy_last = nullptr; float* dy_prev = nullptr;     // CARRY
+    const LmRoute* route = nullptr;                                                             // ROUTED (dout[0]: in routed row order)
+    bool carry() const { return y_prev || dy_last || dy_prev; }
+};
+struct LnMixParts { int G; float *ln, *mu; };                   // the backward's grid and its two runs of partial rows in ws
+
+// One variant's kernel: the forward by M (routed rows: M = 1 only), the backward by its launch bound (routed rows stop at C = 4096: no 1024)
+template <bool PK, bool CARRY, bool ROUTED>
+void ln_mix_fwd_launch(const LnMixFwd& a, const LmPtrs& pm, const LmOuts& po) {
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(ln_grid(a.ntok, LN_MIX_ROWS_PER_WG)), dim3(ln_threads(a.C)), 0, (hipStream_t)a.stream, a.ntok, a.T, a.C, a.eps,
+                           (const uint16_t*)a.x, (const uint16_t*)a.delta, (const uint16_t*)a.w, (const uint16_t*)a.b, (uint16_t*)a.xn, a.mean, a.rstd, pm, po,
+                           a.first, (const uint16_t*)a.y_prev, (uint16_t*)a.y_last, a.route ? *a.route : LmRoute());
+    };
+    if (ROUTED || a.M == 1) go(ln_mix_fwd_kernel<1, PK, CARRY, ROUTED>);
+    else if constexpr (!ROUTED) go(ln_mix_fwd_kernel<6, PK, CARRY, ROUTED>);
+}
+template <bool PK, bool CARRY, bool ROUTED>
+void ln_mix_bwd_launch(const LnMixBwd& a, const LmPtrs& pm, const LmPtrs& pd, const LnMixParts& part) {
+    const int threads = ln_threads(a.C);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(part.G), dim3(threads), 0, (hipStream_t)a.stream, a.ntok, a.T, a.C, (const uint16_t*)a.xn, a.mean, a.rstd,
+                           (const uint16_t*)a.w, (const uint16_t*)a.b, pm, pd, (const uint16_t*)a.dout3_second, (const uint16_t*)a.dres, (uint16_t*)a.dx,
+                           part.ln, part.mu, a.first, (const uint16_t*)a.y_prev, a.dy_last, a.dy_prev, a.route ? *a.route : LmRoute());
+    };
+    if (threads <= 256) go(ln_mix_bwd_kernel<1, false, 256, PK, CARRY, ROUTED>);
+    else if (ROUTED || threads <= 512) go(ln_mix_bwd_kernel<1, false, 512, PK, CARRY, ROUTED>);
+    else if constexpr (!ROUTED) go(ln_mix_bwd_kernel<1, false, 1024, PK, CARRY, ROUTED>);
+}
+// The variant from the fields.  PK with CARRY, and ROUTED with CARRY, are not built: the launchers refuse them before they come here.  Four
+// functions in this order, not two: kernels enter the code object in the order of their first mention, and this is the order they have there.
+void ln_mix_fwd_rows(const LnMixFwd& a, const LmPtrs& pm, const LmOuts& po) {
+    if (a.first) ln_mix_fwd_launch<true, false, false>(a, pm, po);
+    else if (!a.carry()) ln_mix_fwd_launch<false, false, false>(a, pm, po);
+    else ln_mix_fwd_launch<false, true, false>(a, pm, po);
+}
+void ln_mix_bwd_rows(const LnMixBwd& a, const LmPtrs& pm, const LmPtrs& pd, const LnMixParts& part) {
+    if (a.first) ln_mix_bwd_launch<true, false, false>(a, pm, pd, part);
+    else if (!a.carry()) ln_mix_bwd_launch<false, false, false>(a, pm, pd, part);
+    else ln_mix_bwd_launch<false, true, false>(a, pm, pd, part);
+}
+void ln_mix_fwd_routed(const LnMixFwd& a, const LmPtrs& pm, const LmOuts& po) {
+    if (a.first) ln_mix_fwd_launch<true, false, true>(a, pm, po); else ln_mix_fwd_launch<false, false, true>(a, pm, po);
+}
+void ln_mix_bwd_routed(const LnMixBwd& a, const LmPtrs& pm, const LmPtrs& pd, const LnMixParts& part) {
+    if (a.first) ln_mix_bwd_launch<true, false, true>(a, pm, pd, part); else ln_mix_bwd_launch<false, false, true>(a, pm, pd, part);
+}
+
+int ln_mix_fwd(const LnMixFwd& a) {
+    if (a.ntok <= 0 || a.T <= 0 || a.ntok % a.T != 0 || !a.x || !a.w || !a.b || !a.mu || !a.out || !a.mean || !a.rstd || (a.delta && !a.xn)) return VRWKV_EINVAL;
+    if (a.route && (!route_ok(*a.route) || !a.mu[0] || !a.out[0])) return VRWKV_EINVAL;
+    if (a.carry() && (a.first || a.route)) return VRWKV_EINVAL;         // not built
+    if (!ln_ok(a.C) || (a.M != 1 && a.M != 6) || (a.route && (a.M != 1 || a.C > 4096))) return VRWKV_ESHAPE;
+    LmPtrs pm{}; LmOuts po{};
+    for (int j = 0; j < a.M; ++j) {
+        if (!a.mu[j] || !a.out[j]) return VRWKV_EINVAL;
+        pm.p[j] = (const uint16_t*)a.mu[j]; po.p[j] = (uint16_t*)a.out[j];
+    }
+    if (a.route) ln_mix_fwd_routed(a, pm, po); else ln_mix_fwd_rows(a, pm, po);
+    return done();
+}
+
+// ws: G (2 + M) C floats, routed G (4 + 2) C -- the (dgamma, dbeta) partial rows of every workgroup, then its dmu rows
+int ln_mix_bwd(const LnMixBwd& a) {
+    if (a.ntok <= 0 || a.T <= 0 || a.ntok % a.T != 0 || !a.xn || !a.mean || !a.rstd || !a.w || !a.b || !a.mu || !a.dout || !a.dx || !a.dwb || !a.dmu || !a.ws)
+        return VRWKV_EINVAL;
+    if (a.route && (!route_ok(*a.route) || !a.mu[0] || !a.dout[0])) return VRWKV_EINVAL;
+    if (a.carry() && (a.first || a.route)) return VRWKV_EINVAL;         // not built
+    // M = 6: vrwkv_mix_bwd_ln_bf16 / _packed / _carry (tmix_fused.hip) + vrwkv_add_ln_bwd_bf16
+    if (!ln_ok(a.C) || a.M != 1 || a.dout3_second || (a.route && a.C > 4096)) return VRWKV_ESHAPE;
+    if (!a.mu[0] || !a.dout[0]) return VRWKV_EINVAL;
+    LmPtrs pm{}, pd{};
+    pm.p[0] = (const uint16_t*)a.mu[0]; pd.p[0] = (const uint16_t*)a.dout[0];
+    const int G = ln_mix_bwd_grid(a.ntok);
+    const long w_ln = (a.route ? 4L : 2L) * a.C, w_mu = (a.route ? 2L : 1L) * a.C;
+    const LnMixParts part{G, a.ws, a.ws + (size_t)G * w_ln};
+    if (a.route) ln_mix_bwd_routed(a, pm, pd, part); else ln_mix_bwd_rows(a, pm, pd, part);
+    colsum(G, w_ln, part.ln, a.dwb, (hipStream_t)a.stream);
+    colsum(G, w_mu, part.mu, a.dmu, (hipStream_t)a.stream);
+    return done();
+}
 
 }  // namespace
 
@@ -64,8 +171,7 @@ int vrwkv_add_ln_fwd_bf16(long ntok, int C, float eps, const void* x, const void
     hipLaunchKernelGGL(add_ln_fwd_kernel, dim3(ln_grid(ntok)), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, eps,
                        (const uint16_t*)x, (const uint16_t*)delta, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn,
                        (uint16_t*)y, mean, rstd, (const long*)nullptr, (const uint16_t*)nullptr);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return done();
 }
 
 // Inference form for the frozen ViT towers (timm pre-LN blocks, src/vision.py:123-134; SAM blocks, src/sam.py:231-247):
@@ -77,8 +183,7 @@ int vrwkv_add_ln_scaled_fwd_bf16(long ntok, int C, float eps, const void* x, con
     hipLaunchKernelGGL(add_ln_fwd_kernel, dim3(ln_grid(ntok)), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, eps,
                        (const uint16_t*)x, (const uint16_t*)delta, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn,
                        (uint16_t*)y, (float*)nullptr, (float*)nullptr, (const long*)nullptr, (const uint16_t*)dscale);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return done();
 }
 
 // LayerNorm of the projector output written straight into the rows of the token-embedding tensor that hold the image
@@ -93,8 +198,7 @@ int vrwkv_ln_scatter_fwd_bf16(long ntok, int C, float eps, const void* x, const 
     hipLaunchKernelGGL(add_ln_fwd_kernel, dim3(ln_grid(ntok)), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, eps,
                        (const uint16_t*)x, (const uint16_t*)nullptr, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)nullptr,
                        (uint16_t*)out, mean, rstd, row_index, (const uint16_t*)nullptr);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return done();
 }
 
 // ... and its backward: dx[n] = LN'(dout[row_index[n]]), dwb = (dgamma, dbeta); ws as for vrwkv_add_ln_bwd_bf16
@@ -105,9 +209,8 @@ int vrwkv_ln_gather_bwd_bf16(long ntok, int C, const void* dout, const long* row
     const int G = ln_bwd_grid(ntok);
     hipLaunchKernelGGL(add_ln_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, (const uint16_t*)dout,
                        (const uint16_t*)nullptr, (const uint16_t*)x, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws, row_index);
-    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, (hipStream_t)stream, G, 2L * C, ws, dwb);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    colsum(G, 2L * C, ws, dwb, (hipStream_t)stream);
+    return done();
 }
 
 // The visual token compressor's tail: ln_out, unpad, AdaptiveAvgPool1d over tokens and the scatter into the placeholder rows in one pass
@@ -119,8 +222,7 @@ int vrwkv_ln_pool_scatter_fwd_bf16(int B, int T, int pad, int Lout, int C, float
     hipLaunchKernelGGL(ln_pool_fwd_kernel, dim3(ln_pool_grid((long)B * Lout)), dim3(ln_threads(C)), 0, (hipStream_t)stream, B, T, pad, Lout, C, eps,
                        (const uint16_t*)x, (const uint16_t*)delta, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, (uint16_t*)out, mean, rstd,
                        row_index);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return done();
 }
 
 int vrwkv_ln_pool_gather_bwd_bf16(int B, int T, int pad, int Lout, int C, const void* dout, const long* row_index, const void* xn,
@@ -130,9 +232,8 @@ int vrwkv_ln_pool_gather_bwd_bf16(int B, int T, int pad, int Lout, int C, const 
     const int G = ln_bwd_grid((long)B * T);
     hipLaunchKernelGGL(ln_pool_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, B, T, pad, Lout, C, (const uint16_t*)dout, row_index,
                        (const uint16_t*)xn, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws);
-    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, (hipStream_t)stream, G, 2L * C, ws, dwb);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    colsum(G, 2L * C, ws, dwb, (hipStream_t)stream);
+    return done();
 }
 
 int vrwkv_add_ln_bwd_bf16(long ntok, int C, const void* dy, const void* dres, const void* xn, const float* mean,
@@ -142,9 +243,8 @@ int vrwkv_add_ln_bwd_bf16(long ntok, int C, const void* dy, const void* dres, co
     const int G = ln_bwd_grid(ntok);
     hipLaunchKernelGGL(add_ln_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, (const uint16_t*)dy,
                        (const uint16_t*)dres, (const uint16_t*)xn, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws, (const long*)nullptr);
-    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, (hipStream_t)stream, G, 2L * C, ws, dwb);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    colsum(G, 2L * C, ws, dwb, (hipStream_t)stream);
+    return done();
 }
 
 // Residual add + LayerNorm + token shift + M lerps (M = 1: channel-mix, M = 6: time-mix), see ln_mix_fwd_kernel above.
@@ -152,32 +252,14 @@ long vrwkv_ln_mix_ws_floats(long ntok, int C, int M) { return (long)ln_mix_bwd_g
 
 int vrwkv_ln_mix_fwd_bf16(long ntok, int T, int C, float eps, int M, const void* x, const void* delta, const void* w, const void* b,
                           const void* const* mu, void* xn, void* const* out, float* mean, float* rstd, void* stream) {
-    return vrwkv_ln_mix_fwd_packed_bf16(ntok, T, C, eps, M, x, delta, w, b, mu, xn, out, mean, rstd, nullptr, stream);
+    return ln_mix_fwd({ntok, T, C, eps, M, x, delta, w, b, mu, xn, out, mean, rstd, stream});
 }
 
 // the same with sample boundaries inside the rows: first[n] != 0 (ntok bytes) = row n reads zeros for its shifted value; NULL = the entry above
 int vrwkv_ln_mix_fwd_packed_bf16(long ntok, int T, int C, float eps, int M, const void* x, const void* delta, const void* w, const void* b,
                                  const void* const* mu, void* xn, void* const* out, float* mean, float* rstd, const unsigned char* first,
                                  void* stream) {
-    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !x || !w || !b || !mu || !out || !mean || !rstd || (delta && !xn)) return VRWKV_EINVAL;
-    if (!ln_ok(C) || (M != 1 && M != 6)) return VRWKV_ESHAPE;
-    LmPtrs pm{}; LmOuts po{};
-    for (int j = 0; j < M; ++j) {
-        if (!mu[j] || !out[j]) return VRWKV_EINVAL;
-        pm.p[j] = (const uint16_t*)mu[j]; po.p[j] = (uint16_t*)out[j];
-    }
-    const dim3 grid(ln_grid(ntok, LN_MIX_ROWS_PER_WG)), block(ln_threads(C));
-    hipStream_t st = (hipStream_t)stream;
-    if (first && M == 1) hipLaunchKernelGGL((ln_mix_fwd_kernel<1, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
-                                            (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po, first);
-    else if (first) hipLaunchKernelGGL((ln_mix_fwd_kernel<6, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
-                                       (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po, first);
-    else if (M == 1) hipLaunchKernelGGL(ln_mix_fwd_kernel<1>, grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
-                                   (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po);
-    else hipLaunchKernelGGL(ln_mix_fwd_kernel<6>, grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
-                            (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return ln_mix_fwd({ntok, T, C, eps, M, x, delta, w, b, mu, xn, out, mean, rstd, stream, first});
 }
 
 // the same for one segment of a longer row (training across a cut): y_prev (B, C) bf16 = the LayerNorm output of the row before each sample's
@@ -186,24 +268,7 @@ int vrwkv_ln_mix_fwd_packed_bf16(long ntok, int T, int C, float eps, int M, cons
 int vrwkv_ln_mix_fwd_carry_bf16(long ntok, int T, int C, float eps, int M, const void* x, const void* delta, const void* w, const void* b,
                                 const void* const* mu, void* xn, void* const* out, float* mean, float* rstd, const void* y_prev, void* y_last,
                                 void* stream) {
-    if (!y_prev && !y_last) return vrwkv_ln_mix_fwd_packed_bf16(ntok, T, C, eps, M, x, delta, w, b, mu, xn, out, mean, rstd, nullptr, stream);
-    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !x || !w || !b || !mu || !out || !mean || !rstd || (delta && !xn)) return VRWKV_EINVAL;
-    if (!ln_ok(C) || (M != 1 && M != 6)) return VRWKV_ESHAPE;
-    LmPtrs pm{}; LmOuts po{};
-    for (int j = 0; j < M; ++j) {
-        if (!mu[j] || !out[j]) return VRWKV_EINVAL;
-        pm.p[j] = (const uint16_t*)mu[j]; po.p[j] = (uint16_t*)out[j];
-    }
-    const dim3 grid(ln_grid(ntok, LN_MIX_ROWS_PER_WG)), block(ln_threads(C));
-    hipStream_t st = (hipStream_t)stream;
-    if (M == 1) hipLaunchKernelGGL((ln_mix_fwd_kernel<1, false, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
-                                   (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po, (const unsigned char*)nullptr,
-                                   (const uint16_t*)y_prev, (uint16_t*)y_last);
-    else hipLaunchKernelGGL((ln_mix_fwd_kernel<6, false, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, (const uint16_t*)delta,
-                            (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, mean, rstd, pm, po, (const unsigned char*)nullptr,
-                            (const uint16_t*)y_prev, (uint16_t*)y_last);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return ln_mix_fwd({ntok, T, C, eps, M, x, delta, w, b, mu, xn, out, mean, rstd, stream, nullptr, y_prev, y_last});
 }
 
 // dx = dres + LN'(gradient of the lerps' input), dwb = (dgamma, dbeta) (2, C) fp32, dmu (M, C) fp32; dres may be NULL;
@@ -213,35 +278,14 @@ int vrwkv_ln_mix_fwd_carry_bf16(long ntok, int T, int C, float eps, int M, const
 int vrwkv_ln_mix_bwd_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* w,
                           const void* b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* dres,
                           void* dx, float* dwb, float* dmu, float* ws, void* stream) {
-    return vrwkv_ln_mix_bwd_packed_bf16(ntok, T, C, M, xn, mean, rstd, w, b, mu, dout, dout3_second, dres, nullptr, dx, dwb, dmu, ws, stream);
+    return ln_mix_bwd({ntok, T, C, M, xn, mean, rstd, w, b, mu, dout, dout3_second, dres, dx, dwb, dmu, ws, stream});
 }
 
 // the same with sample boundaries inside the rows: first[n] != 0 (ntok bytes) = no gradient from row n to row n-1; NULL = the entry above
 int vrwkv_ln_mix_bwd_packed_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* w,
                                  const void* b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* dres,
                                  const unsigned char* first, void* dx, float* dwb, float* dmu, float* ws, void* stream) {
-    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !xn || !mean || !rstd || !w || !b || !mu || !dout || !dx || !dwb || !dmu || !ws) return VRWKV_EINVAL;
-    if (!ln_ok(C) || M != 1 || dout3_second) return VRWKV_ESHAPE;        // M = 6: vrwkv_mix_bwd_ln_bf16 + vrwkv_add_ln_bwd_bf16 (below)
-    LmPtrs pm{}, pd{};
-    for (int j = 0; j < M; ++j) {
-        if (!mu[j] || !dout[j]) return VRWKV_EINVAL;
-        pm.p[j] = (const uint16_t*)mu[j]; pd.p[j] = (const uint16_t*)dout[j];
-    }
-    const int G = ln_mix_bwd_grid(ntok);
-    const dim3 grid(G), block(ln_threads(C));
-    hipStream_t st = (hipStream_t)stream;
-    float* part_ln = ws; float* part_mu = ws + (size_t)G * 2 * C;
-#define LN_MIX_BWD_LB(MM, DUP, LB, PK) hipLaunchKernelGGL((ln_mix_bwd_kernel<MM, DUP, LB, PK>), grid, block, 0, st, ntok, T, C, (const uint16_t*)xn, mean, rstd, \
-        (const uint16_t*)w, (const uint16_t*)b, pm, pd, (const uint16_t*)dout3_second, (const uint16_t*)dres, (uint16_t*)dx, part_ln, part_mu, first)
-#define LN_MIX_BWD(MM, DUP, PK) do { if (block.x <= 256) LN_MIX_BWD_LB(MM, DUP, 256, PK); else if (block.x <= 512) LN_MIX_BWD_LB(MM, DUP, 512, PK); \
-                                     else LN_MIX_BWD_LB(MM, DUP, 1024, PK); } while (0)
-    if (first) LN_MIX_BWD(1, false, true); else LN_MIX_BWD(1, false, false);
-#undef LN_MIX_BWD
-#undef LN_MIX_BWD_LB
-    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, st, G, 2L * C, part_ln, dwb);
-    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)((long)M * C / 16)), dim3(256), 0, st, G, (long)M * C, part_mu, dmu);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return ln_mix_bwd({ntok, T, C, M, xn, mean, rstd, w, b, mu, dout, dout3_second, dres, dx, dwb, dmu, ws, stream, first});
 }
 
 // the channel-mix backward for one segment of a longer row: y_prev as in the forward; dy_last (B, C) fp32 = the gradient the next segment sends
@@ -251,26 +295,7 @@ int vrwkv_ln_mix_bwd_carry_bf16(long ntok, int T, int C, int M, const void* xn, 
                                 const void* b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* dres,
                                 const void* y_prev, const float* dy_last, float* dy_prev, void* dx, float* dwb, float* dmu, float* ws,
                                 void* stream) {
-    if (!y_prev && !dy_last && !dy_prev)
-        return vrwkv_ln_mix_bwd_packed_bf16(ntok, T, C, M, xn, mean, rstd, w, b, mu, dout, dout3_second, dres, nullptr, dx, dwb, dmu, ws, stream);
-    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !xn || !mean || !rstd || !w || !b || !mu || !dout || !dx || !dwb || !dmu || !ws) return VRWKV_EINVAL;
-    if (!ln_ok(C) || M != 1 || dout3_second) return VRWKV_ESHAPE;        // M = 6: vrwkv_mix_bwd_ln_carry_bf16 + vrwkv_add_ln_bwd_bf16
-    if (!mu[0] || !dout[0]) return VRWKV_EINVAL;
-    LmPtrs pm{}, pd{};
-    pm.p[0] = (const uint16_t*)mu[0]; pd.p[0] = (const uint16_t*)dout[0];
-    const int G = ln_mix_bwd_grid(ntok);
-    const dim3 grid(G), block(ln_threads(C));
-    hipStream_t st = (hipStream_t)stream;
-    float* part_ln = ws; float* part_mu = ws + (size_t)G * 2 * C;
-#define LN_MIX_BWD_CARRY(LB) hipLaunchKernelGGL((ln_mix_bwd_kernel<1, false, LB, false, true>), grid, block, 0, st, ntok, T, C, (const uint16_t*)xn, mean, rstd, \
-        (const uint16_t*)w, (const uint16_t*)b, pm, pd, (const uint16_t*)nullptr, (const uint16_t*)dres, (uint16_t*)dx, part_ln, part_mu,                       \
-        (const unsigned char*)nullptr, (const uint16_t*)y_prev, dy_last, dy_prev)
-    if (block.x <= 256) LN_MIX_BWD_CARRY(256); else if (block.x <= 512) LN_MIX_BWD_CARRY(512); else LN_MIX_BWD_CARRY(1024);
-#undef LN_MIX_BWD_CARRY
-    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, st, G, 2L * C, part_ln, dwb);
-    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)((long)M * C / 16)), dim3(256), 0, st, G, (long)M * C, part_mu, dmu);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return ln_mix_bwd({ntok, T, C, M, xn, mean, rstd, w, b, mu, dout, dout3_second, dres, dx, dwb, dmu, ws, stream, nullptr, y_prev, dy_last, dy_prev});
 }
 
 // Modality-routed channel mix (a Block with ln_v / ffn_v for image tokens, VisualRWKV-v7/v7.10/src/model.py:233-262): every row goes through ONE
@@ -280,21 +305,9 @@ int vrwkv_ln_mix_bwd_carry_bf16(long ntok, int T, int C, int M, const void* xn, 
 int vrwkv_ln_mix_routed_fwd_bf16(long ntok, int T, int C, float eps, const void* x, const void* delta, const void* const* w, const void* const* b,
                                  const void* const* mu, void* xn, void* out, float* mean, float* rstd, const unsigned char* first,
                                  const unsigned char* sel, const void* pos, int pos_bytes, void* stream) {
-    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !x || !w || !b || !mu || !out || !mean || !rstd || !sel || !pos || (delta && !xn)) return VRWKV_EINVAL;
-    if (!w[0] || !w[1] || !b[0] || !b[1] || !mu[0] || !mu[1] || (pos_bytes != 4 && pos_bytes != 8)) return VRWKV_EINVAL;
-    if (!ln_ok(C) || C > 4096) return VRWKV_ESHAPE;
-    LmPtrs pm{}; LmOuts po{};
-    pm.p[0] = (const uint16_t*)mu[0]; po.p[0] = (uint16_t*)out;
+    if (!w || !b || !mu || (pos_bytes != 4 && pos_bytes != 8)) return VRWKV_EINVAL;      // read here; what they hold is the launcher's to check
     const LmRoute rt{(const uint16_t*)w[1], (const uint16_t*)b[1], (const uint16_t*)mu[1], sel, pos, pos_bytes == 8};
-    const dim3 grid(ln_grid(ntok, LN_MIX_ROWS_PER_WG)), block(ln_threads(C));
-    hipStream_t st = (hipStream_t)stream;
-#define LN_MIX_FWD_ROUTED(PK) hipLaunchKernelGGL((ln_mix_fwd_kernel<1, PK, false, true>), grid, block, 0, st, ntok, T, C, eps, (const uint16_t*)x, \
-        (const uint16_t*)delta, (const uint16_t*)w[0], (const uint16_t*)b[0], (uint16_t*)xn, mean, rstd, pm, po, first, (const uint16_t*)nullptr,    \
-        (uint16_t*)nullptr, rt)
-    if (first) LN_MIX_FWD_ROUTED(true); else LN_MIX_FWD_ROUTED(false);
-#undef LN_MIX_FWD_ROUTED
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return ln_mix_fwd({ntok, T, C, eps, 1, x, delta, w[0], b[0], mu, xn, &out, mean, rstd, stream, first, nullptr, nullptr, &rt});
 }
 
 // its backward: dout (ntok, C) in pos order; dx (ntok, C) in token order = dres + LN'(..) with the row's shared statistics; dwb (2, 2, C) fp32 =
@@ -306,27 +319,9 @@ int vrwkv_ln_mix_routed_bwd_bf16(long ntok, int T, int C, const void* xn, const 
                                  const void* const* b, const void* const* mu, const void* dout, const void* dres, const unsigned char* first,
                                  const unsigned char* sel, const void* pos, int pos_bytes, void* dx, float* dwb, float* dmu, float* ws,
                                  void* stream) {
-    if (ntok <= 0 || T <= 0 || ntok % T != 0 || !xn || !mean || !rstd || !w || !b || !mu || !dout || !sel || !pos || !dx || !dwb || !dmu || !ws) return VRWKV_EINVAL;
-    if (!w[0] || !w[1] || !b[0] || !b[1] || !mu[0] || !mu[1] || (pos_bytes != 4 && pos_bytes != 8)) return VRWKV_EINVAL;
-    if (!ln_ok(C) || C > 4096) return VRWKV_ESHAPE;
-    LmPtrs pm{}, pd{};
-    pm.p[0] = (const uint16_t*)mu[0]; pd.p[0] = (const uint16_t*)dout;
+    if (!w || !b || !mu || (pos_bytes != 4 && pos_bytes != 8)) return VRWKV_EINVAL;      // as in the forward
     const LmRoute rt{(const uint16_t*)w[1], (const uint16_t*)b[1], (const uint16_t*)mu[1], sel, pos, pos_bytes == 8};
-    const int G = ln_mix_bwd_grid(ntok);
-    const dim3 grid(G), block(ln_threads(C));
-    hipStream_t st = (hipStream_t)stream;
-    float* part_ln = ws; float* part_mu = ws + (size_t)G * 4 * C;
-#define LN_MIX_BWD_ROUTED_LB(LB, PK) hipLaunchKernelGGL((ln_mix_bwd_kernel<1, false, LB, PK, false, true>), grid, block, 0, st, ntok, T, C, (const uint16_t*)xn, mean, \
-        rstd, (const uint16_t*)w[0], (const uint16_t*)b[0], pm, pd, (const uint16_t*)nullptr, (const uint16_t*)dres, (uint16_t*)dx, part_ln, part_mu, first,        \
-        (const uint16_t*)nullptr, (const float*)nullptr, (float*)nullptr, rt)
-#define LN_MIX_BWD_ROUTED(PK) do { if (block.x <= 256) LN_MIX_BWD_ROUTED_LB(256, PK); else LN_MIX_BWD_ROUTED_LB(512, PK); } while (0)
-    if (first) LN_MIX_BWD_ROUTED(true); else LN_MIX_BWD_ROUTED(false);
-#undef LN_MIX_BWD_ROUTED
-#undef LN_MIX_BWD_ROUTED_LB
-    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(4L * C / 16)), dim3(256), 0, st, G, 4L * C, part_ln, dwb);
-    hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(2L * C / 16)), dim3(256), 0, st, G, 2L * C, part_mu, dmu);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return ln_mix_bwd({ntok, T, C, 1, xn, mean, rstd, w[0], b[0], mu, &dout, nullptr, dres, dx, dwb, dmu, ws, stream, first, nullptr, nullptr, nullptr, &rt});
 }
 
 // dst[i] = src[idx[i]] for i < n on rows of C bf16 (C % 8 == 0); idx: n int32 (idx_bytes 4) or int64 (8) on the device, every entry a row of src
@@ -338,8 +333,7 @@ int vrwkv_row_gather_bf16(long n, int C, const void* src, const void* idx, int i
     const dim3 grid((unsigned)(g > (1L << 20) ? (1L << 20) : g)), block(256);
     if (idx_bytes == 8) hipLaunchKernelGGL(row_gather_kernel<true>, grid, block, 0, (hipStream_t)stream, nvec, C / 8, (const uint16_t*)src, idx, (uint16_t*)dst);
     else hipLaunchKernelGGL(row_gather_kernel<false>, grid, block, 0, (hipStream_t)stream, nvec, C / 8, (const uint16_t*)src, idx, (uint16_t*)dst);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return done();
 }
 
 }  // extern "C"

@@ -756,18 +756,13 @@ int vrwkv_mix_bwd2_bf16(long ntok, int T, int C, int M, const void* x, const voi
     return done();
 }
 
-// mix backward when x is the (unstored) LayerNorm output of vrwkv_ln_mix_fwd_bf16: recomputed from xn, mean, rstd, ln_w, ln_b
-int vrwkv_mix_bwd_ln_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
-                          const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second, void* dx,
-                          float* dmu, float* ws, void* stream) {
-    return vrwkv_mix_bwd_ln_packed_bf16(ntok, T, C, M, xn, mean, rstd, ln_w, ln_b, mu, dout, dout3_second, nullptr, dx, dmu, ws, stream);
-}
-
-// the same with sample boundaries inside the rows: first[n] != 0 (ntok bytes) = no gradient from row n to row n-1; NULL = the entry above
-int vrwkv_mix_bwd_ln_packed_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
-                                 const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second,
-                                 const unsigned char* first, void* dx, float* dmu, float* ws, void* stream) {
-    if (ntok <= 0 || T <= 0 || !xn || !mean || !rstd || !ln_w || !ln_b || !mu || !dout || !dx || !dmu || !ws || M != 6) return VRWKV_EINVAL;
+// vrwkv_mix_bwd_ln_bf16 / _packed / _carry: one launch, the variant from the optional pointers -- first: PK; y_prev, dy_last, dy_prev: CARRY; the two
+// together are not built.  (Here and not in the namespace above: kernels enter the code object in the order of their first mention.)
+static int mix_bwd_ln(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w, const void* ln_b,
+                      const void* const* mu, const void* const* dout, const void* dout3_second, const unsigned char* first, const void* y_prev,
+                      const float* dy_last, float* dy_prev, void* dx, float* dmu, float* ws, void* stream) {
+    const bool carry = y_prev || dy_last || dy_prev;
+    if (ntok <= 0 || T <= 0 || !xn || !mean || !rstd || !ln_w || !ln_b || !mu || !dout || !dx || !dmu || !ws || M != 6 || (first && carry)) return VRWKV_EINVAL;
     if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
     Ptrs6 m{}, d{};
     for (int i = 0; i < M; ++i) { m.p[i] = (const uint16_t*)mu[i]; d.p[i] = (const uint16_t*)dout[i]; if (!m.p[i] || !d.p[i]) return VRWKV_EINVAL; }
@@ -776,12 +771,32 @@ int vrwkv_mix_bwd_ln_packed_bf16(long ntok, int T, int C, int M, const void* xn,
     const int threads = C / 4 < 512 ? C / 4 : 512;
     const uint16_t* d2 = (const uint16_t*)dout3_second;
     const LnX ln{mean, rstd, (const uint16_t*)ln_w, (const uint16_t*)ln_b};
-    if (first && d2) hipLaunchKernelGGL((mix_bwd_kernel<6, true, false, true, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln, first);
-    else if (first) hipLaunchKernelGGL((mix_bwd_kernel<6, false, false, true, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln, first);
-    else if (d2) hipLaunchKernelGGL((mix_bwd_kernel<6, true, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln);
-    else hipLaunchKernelGGL((mix_bwd_kernel<6, false, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln, first,
+                           (const uint16_t*)y_prev, dy_last, dy_prev);
+    };
+    if (first && d2) go(mix_bwd_kernel<6, true, false, true, true>);
+    else if (first) go(mix_bwd_kernel<6, false, false, true, true>);
+    else if (!carry && d2) go(mix_bwd_kernel<6, true, false, true>);
+    else if (!carry) go(mix_bwd_kernel<6, false, false, true>);
+    else if (d2) go(mix_bwd_kernel<6, true, false, true, false, true>);
+    else go(mix_bwd_kernel<6, false, false, true, false, true>);
     colsum(G, (long)M * C, ws, dmu, st);
     return done();
+}
+
+// mix backward when x is the (unstored) LayerNorm output of vrwkv_ln_mix_fwd_bf16: recomputed from xn, mean, rstd, ln_w, ln_b
+int vrwkv_mix_bwd_ln_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
+                          const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second, void* dx,
+                          float* dmu, float* ws, void* stream) {
+    return mix_bwd_ln(ntok, T, C, M, xn, mean, rstd, ln_w, ln_b, mu, dout, dout3_second, nullptr, nullptr, nullptr, nullptr, dx, dmu, ws, stream);
+}
+
+// the same with sample boundaries inside the rows: first[n] != 0 (ntok bytes) = no gradient from row n to row n-1; NULL = the entry above
+int vrwkv_mix_bwd_ln_packed_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
+                                 const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second,
+                                 const unsigned char* first, void* dx, float* dmu, float* ws, void* stream) {
+    return mix_bwd_ln(ntok, T, C, M, xn, mean, rstd, ln_w, ln_b, mu, dout, dout3_second, first, nullptr, nullptr, nullptr, dx, dmu, ws, stream);
 }
 
 // the same for one segment of a longer row (training across a cut): y_prev (B, C) bf16 = the LayerNorm output of the row before each sample's
@@ -790,23 +805,7 @@ int vrwkv_mix_bwd_ln_packed_bf16(long ntok, int T, int C, int M, const void* xn,
 int vrwkv_mix_bwd_ln_carry_bf16(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w,
                                 const void* ln_b, const void* const* mu, const void* const* dout, const void* dout3_second, const void* y_prev,
                                 const float* dy_last, float* dy_prev, void* dx, float* dmu, float* ws, void* stream) {
-    if (!y_prev && !dy_last && !dy_prev)
-        return vrwkv_mix_bwd_ln_packed_bf16(ntok, T, C, M, xn, mean, rstd, ln_w, ln_b, mu, dout, dout3_second, nullptr, dx, dmu, ws, stream);
-    if (ntok <= 0 || T <= 0 || !xn || !mean || !rstd || !ln_w || !ln_b || !mu || !dout || !dx || !dmu || !ws || M != 6) return VRWKV_EINVAL;
-    if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
-    Ptrs6 m{}, d{};
-    for (int i = 0; i < M; ++i) { m.p[i] = (const uint16_t*)mu[i]; d.p[i] = (const uint16_t*)dout[i]; if (!m.p[i] || !d.p[i]) return VRWKV_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    const int G = bwd_grid(ntok);
-    const int threads = C / 4 < 512 ? C / 4 : 512;
-    const uint16_t* d2 = (const uint16_t*)dout3_second;
-    const LnX ln{mean, rstd, (const uint16_t*)ln_w, (const uint16_t*)ln_b};
-    if (d2) hipLaunchKernelGGL((mix_bwd_kernel<6, true, false, true, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws,
-                               Ptrs6{}, MPtrs6{}, ln, (const unsigned char*)nullptr, (const uint16_t*)y_prev, dy_last, dy_prev);
-    else hipLaunchKernelGGL((mix_bwd_kernel<6, false, false, true, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws,
-                            Ptrs6{}, MPtrs6{}, ln, (const unsigned char*)nullptr, (const uint16_t*)y_prev, dy_last, dy_prev);
-    colsum(G, (long)M * C, ws, dmu, st);
-    return done();
+    return mix_bwd_ln(ntok, T, C, M, xn, mean, rstd, ln_w, ln_b, mu, dout, dout3_second, nullptr, y_prev, dy_last, dy_prev, dx, dmu, ws, stream);
 }
 
 // RWKV-6 data-dependent token shift (VisualRWKV-v6/v6.0/src/model.py:150-160): out_j = x + (x[t-1] - x) (mu_j + mm_j), j < 5.

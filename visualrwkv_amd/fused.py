@@ -553,24 +553,55 @@ post = _Post.apply
 relu_sq = _ReluSq.apply
 
 
+def _ln_fwd_pre(who, x, delta, params, first=None):
+    """What the add + LayerNorm forwards share: the inputs contiguous and checked (params: w, b and any lerp weights, each as a (C) row), `first` (the
+    marks of packed rows) checked, xn -- x itself without a delta -- and the row statistics to be filled.
+    Returns (x, delta, params, xn, mean, rstd)."""
+    C = x.shape[-1]
+    x = x.contiguous()
+    delta = delta.contiguous() if delta is not None else None
+    params = [p.reshape(C).contiguous() for p in params]
+    _chk(x, delta, *params)
+    ntok = x.numel() // C
+    if first is not None and (first.dtype != torch.uint8 or first.numel() != ntok or first.device != x.device or not first.is_contiguous()):
+        raise ValueError(f"{who}: `first` must be a contiguous uint8 tensor of {ntok} marks on {x.device}")
+    xn = torch.empty_like(x) if delta is not None else x
+    mean = torch.empty(ntok, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(ntok, dtype=torch.float32, device=x.device)
+    return x, delta, params, xn, mean, rstd
+
+
+def _add_ln_bwd(dy, d_xn, xn, mean, rstd, wc):
+    """The LayerNorm's own backward (vrwkv_add_ln_bwd_bf16): (dx, dwb) = (d_xn + LN'(dy), the fp32 (dgamma, dbeta)); d_xn may be None."""
+    C = xn.shape[-1]
+    ntok = xn.numel() // C
+    dx = torch.empty_like(xn)
+    dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
+    lib = hip_lib.load()
+    ws = torch.empty(lib.vrwkv_add_ln_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
+    rc = lib.vrwkv_add_ln_bwd_bf16(ntok, C, dy.data_ptr(), _p(d_xn), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                   wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
+    hip_lib.check(rc, "vrwkv_add_ln_bwd_bf16")
+    return dx, dwb
+
+
+def _param_grads(dwb, dmu, wc, xn, mu_shapes):
+    """The fp32 parameter gradients in the parameters' dtypes and shapes: (dwb, [dmu_j])."""
+    dmu = dmu.to(xn.dtype)
+    return dwb.to(wc.dtype), [dmu[i].view(sh) for i, sh in enumerate(mu_shapes)]
+
+
 class _AddLN(torch.autograd.Function):
     """(xn, y) = (x + delta, LayerNorm(x + delta));  with delta None: y = LayerNorm(x) only (csrc/ln_fused.hip)."""
 
     @staticmethod
     def forward(ctx, x, delta, w, b, eps):
-        C = x.shape[-1]
-        x = x.contiguous()
-        delta = delta.contiguous() if delta is not None else None
-        wc, bc = w.contiguous(), b.contiguous()
-        _chk(x, delta, wc, bc)
         if delta is not None and delta.shape != x.shape:
             raise ValueError("add_ln: x and delta must have the same shape")
-        ntok = x.numel() // C
-        xn = torch.empty_like(x) if delta is not None else x
+        x, delta, (wc, bc), xn, mean, rstd = _ln_fwd_pre("add_ln", x, delta, (w, b))
+        C = x.shape[-1]
         y = torch.empty_like(x)
-        mean = torch.empty(ntok, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(ntok, dtype=torch.float32, device=x.device)
-        rc = hip_lib.load().vrwkv_add_ln_fwd_bf16(ntok, C, float(eps), x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
+        rc = hip_lib.load().vrwkv_add_ln_fwd_bf16(x.numel() // C, C, float(eps), x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
                                                   xn.data_ptr() if delta is not None else 0, y.data_ptr(),
                                                   mean.data_ptr(), rstd.data_ptr(), _stream(x))
         hip_lib.check(rc, "vrwkv_add_ln_fwd_bf16")
@@ -584,18 +615,10 @@ class _AddLN(torch.autograd.Function):
     def backward(ctx, *grads):
         xn, mean, rstd, wc = ctx.saved_tensors
         d_xn, dy = grads if ctx.has_delta else (None, grads[0])
-        C = xn.shape[-1]
-        ntok = xn.numel() // C
         dy = dy.contiguous()
         d_xn = d_xn.contiguous() if d_xn is not None else None
         _chk(dy, d_xn)
-        dx = torch.empty_like(xn)
-        dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
-        lib = hip_lib.load()
-        ws = torch.empty(lib.vrwkv_add_ln_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
-        rc = lib.vrwkv_add_ln_bwd_bf16(ntok, C, dy.data_ptr(), _p(d_xn), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                       wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
-        hip_lib.check(rc, "vrwkv_add_ln_bwd_bf16")
+        dx, dwb = _add_ln_bwd(dy, d_xn, xn, mean, rstd, wc)
         dwb = dwb.to(wc.dtype)
         return dx, (dx if ctx.has_delta else None), dwb[0], dwb[1], None
 
@@ -628,152 +651,81 @@ class _AddLnMix(torch.autograd.Function):
     kernel each way (csrc/ln_fused.hip: ln_mix_*): the LayerNorm output is never written.  M = 1 (channel-mix) or 6 (time-mix);
     dup3: a 7th output aliasing output 3 (x_v) for its second consumer, as `_MixDup3`.  delta may be None (first block).
     first: None, or the (B*T) uint8 marks of a wkv7.PackedLayout (rows that hold several samples end to end): the _packed entries then
-    shift zeros into every sample's first token and send no gradient from it to the row before."""
+    shift zeros into every sample's first token and send no gradient from it to the row before.
+    y_prev, want_last: x is one segment of a longer row (training across a cut; the _carry entries of csrc/ln_fused.hip / tmix_fused.hip) and
+    the result is (xn, out_0 .. out_{M-1}[, alias of out_3], y_last).  y_prev (B, C), or None = zeros: the LayerNorm output of the token before
+    the segment, which the shift reads at t = 0; it may require a gradient.  y_last (B, C): the LayerNorm output of the segment's last token, a
+    differentiable output.  y_last is returned in fp32 (it holds bf16 values): its gradient -- the next segment's gradient of y_prev -- then
+    stays fp32 between the two kernels, which add it in fp32 and round once, as they do inside a row.  Not together with `first`."""
 
     @staticmethod
-    def forward(ctx, x, delta, w, b, eps, dup3, first, *mus):
+    def forward(ctx, x, delta, w, b, eps, dup3, first, y_prev, want_last, *mus):
         B, T, C = x.shape
         M = len(mus)
-        x = x.contiguous()
-        delta = delta.contiguous() if delta is not None else None
-        wc, bc = w.contiguous(), b.contiguous()
-        mus_c = [m.reshape(C).contiguous() for m in mus]
-        _chk(x, delta, wc, bc, *mus_c)
-        ntok = B * T
-        xn = torch.empty_like(x) if delta is not None else x
-        outs = [torch.empty_like(x) for _ in mus]
-        mean = torch.empty(ntok, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(ntok, dtype=torch.float32, device=x.device)
-        if first is not None and (first.dtype != torch.uint8 or first.numel() != ntok or first.device != x.device or not first.is_contiguous()):
-            raise ValueError(f"add_ln_mix: `first` must be a contiguous uint8 tensor of {ntok} marks on {x.device}")
-        rc = hip_lib.load().vrwkv_ln_mix_fwd_packed_bf16(ntok, T, C, float(eps), M, x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
-                                                         _ptr_array(mus_c), xn.data_ptr() if delta is not None else 0, _ptr_array(outs),
-                                                         mean.data_ptr(), rstd.data_ptr(), _p(first), _stream(x))
-        hip_lib.check(rc, "vrwkv_ln_mix_fwd_packed_bf16")
-        ctx.first = first
-        ctx.save_for_backward(xn, mean, rstd, wc, bc, *mus_c)
-        ctx.has_delta = delta is not None
-        ctx.mu_shapes = [m.shape for m in mus]
-        if dup3:
-            outs.append(outs[3].view_as(outs[3]))
-        return (xn, *outs)
-
-    @staticmethod
-    def backward(ctx, d_xn, *douts):
-        xn, mean, rstd, wc, bc, *mus_c = ctx.saved_tensors
-        B, T, C = xn.shape
-        M = len(mus_c)
-        douts = [d.contiguous() for d in douts]
-        d_xn = d_xn.contiguous() if d_xn is not None else None
-        _chk(d_xn, *douts)
-        second = douts[M] if len(douts) > M else None
-        ntok = B * T
-        dx = torch.empty_like(xn)
-        dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
-        dmu = torch.empty(M, C, dtype=torch.float32, device=xn.device)
-        lib = hip_lib.load()
-        if M == 1:
-            ws = torch.empty(lib.vrwkv_ln_mix_ws_floats(ntok, C, M), dtype=torch.float32, device=xn.device)
-            rc = lib.vrwkv_ln_mix_bwd_packed_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
-                                                  _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), _p(d_xn), _p(ctx.first), dx.data_ptr(),
-                                                  dwb.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, "vrwkv_ln_mix_bwd_packed_bf16")
-        else:       # six lerps: their backward with the LayerNorm output recomputed in place of a stored one, then the LayerNorm's
-            dy = torch.empty_like(xn)
-            ws = _ws(ntok, C, M, xn.device)
-            rc = lib.vrwkv_mix_bwd_ln_packed_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
-                                                  _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), _p(ctx.first), dy.data_ptr(),
-                                                  dmu.data_ptr(), ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, "vrwkv_mix_bwd_ln_packed_bf16")
-            ws = torch.empty(lib.vrwkv_add_ln_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
-            rc = lib.vrwkv_add_ln_bwd_bf16(ntok, C, dy.data_ptr(), _p(d_xn), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                           wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, "vrwkv_add_ln_bwd_bf16")
-        dwb = dwb.to(wc.dtype)
-        dmu = dmu.to(xn.dtype)
-        return (dx, (dx if ctx.has_delta else None), dwb[0], dwb[1], None, None, None, *[dmu[i].view(sh) for i, sh in enumerate(ctx.mu_shapes)])
-
-
-class _AddLnMixCarry(torch.autograd.Function):
-    """`_AddLnMix` for one segment of a longer row (training across a cut; the _carry entries of csrc/ln_fused.hip / tmix_fused.hip):
-    (xn, out_0 .. out_{M-1}[, alias of out_3], y_last) from (x, delta, y_prev).  y_prev (B, C), or None = zeros: the LayerNorm output of the
-    token before the segment, which the shift reads at t = 0; it may require a gradient.  y_last (B, C): the LayerNorm output of the
-    segment's last token, a differentiable output.  y_last is returned in fp32 (it holds bf16 values): its gradient -- the next segment's
-    gradient of y_prev -- then stays fp32 between the two kernels, which add it in fp32 and round once, as they do inside a row."""
-
-    @staticmethod
-    def forward(ctx, x, delta, w, b, eps, dup3, y_prev, *mus):
-        B, T, C = x.shape
-        M = len(mus)
-        x = x.contiguous()
-        delta = delta.contiguous() if delta is not None else None
-        wc, bc = w.contiguous(), b.contiguous()
-        mus_c = [m.reshape(C).contiguous() for m in mus]
+        carry = want_last or y_prev is not None
+        if carry and first is not None:
+            raise NotImplementedError("add_ln_mix: a carry together with packed rows")
         yp = None
         if y_prev is not None:
             if tuple(y_prev.shape) != (B, C) or y_prev.device != x.device:
                 raise ValueError(f"add_ln_mix: y_prev must be ({B}, {C}) on {x.device}, got {tuple(y_prev.shape)} on {y_prev.device}")
             yp = y_prev.detach().to(torch.bfloat16).contiguous()
-        _chk(x, delta, wc, bc, yp, *mus_c)
-        ntok = B * T
-        xn = torch.empty_like(x) if delta is not None else x
+        x, delta, (wc, bc, *mus_c), xn, mean, rstd = _ln_fwd_pre("add_ln_mix", x, delta, (w, b, *mus), first)
+        _chk(yp)
         outs = [torch.empty_like(x) for _ in mus]
-        mean = torch.empty(ntok, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(ntok, dtype=torch.float32, device=x.device)
-        y_last = torch.empty(B, C, dtype=torch.bfloat16, device=x.device)
-        rc = hip_lib.load().vrwkv_ln_mix_fwd_carry_bf16(ntok, T, C, float(eps), M, x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
-                                                        _ptr_array(mus_c), xn.data_ptr() if delta is not None else 0, _ptr_array(outs),
-                                                        mean.data_ptr(), rstd.data_ptr(), _p(yp), y_last.data_ptr(), _stream(x))
-        hip_lib.check(rc, "vrwkv_ln_mix_fwd_carry_bf16")
+        y_last = torch.empty(B, C, dtype=torch.bfloat16, device=x.device) if want_last else None
+        lib = hip_lib.load()
+        head = (B * T, T, C, float(eps), M, x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(), _ptr_array(mus_c),
+                xn.data_ptr() if delta is not None else 0, _ptr_array(outs), mean.data_ptr(), rstd.data_ptr())
+        if carry:
+            hip_lib.check(lib.vrwkv_ln_mix_fwd_carry_bf16(*head, _p(yp), _p(y_last), _stream(x)), "vrwkv_ln_mix_fwd_carry_bf16")
+        else:
+            hip_lib.check(lib.vrwkv_ln_mix_fwd_packed_bf16(*head, _p(first), _stream(x)), "vrwkv_ln_mix_fwd_packed_bf16")
         ctx.save_for_backward(xn, mean, rstd, wc, bc, *mus_c, *([yp] if yp is not None else []))
-        ctx.has_prev = yp is not None
+        ctx.first, ctx.carry, ctx.want_last, ctx.has_prev = first, carry, want_last, yp is not None
         ctx.prev_dtype = y_prev.dtype if y_prev is not None else None
         ctx.has_delta = delta is not None
         ctx.mu_shapes = [m.shape for m in mus]
-        ctx.M = M
         if dup3:
             outs.append(outs[3].view_as(outs[3]))
-        return (xn, *outs, y_last.float())
+        return (xn, *outs, y_last.float()) if want_last else (xn, *outs)
 
     @staticmethod
-    def backward(ctx, d_xn, *grads):
-        M = ctx.M
+    def backward(ctx, d_xn, *douts):
+        M = len(ctx.mu_shapes)
         xn, mean, rstd, wc, bc, *rest = ctx.saved_tensors
         mus_c, yp = rest[:M], (rest[M] if ctx.has_prev else None)
-        *douts, dy_last = grads
+        dy_last = None
+        if ctx.want_last:
+            *douts, dy_last = douts
+            dy_last = dy_last.float().contiguous()
         B, T, C = xn.shape
         douts = [d.contiguous() for d in douts]
         d_xn = d_xn.contiguous() if d_xn is not None else None
         _chk(d_xn, *douts)
-        dy_last = dy_last.float().contiguous()
         second = douts[M] if len(douts) > M else None
         ntok = B * T
-        dx = torch.empty_like(xn)
-        dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
         dmu = torch.empty(M, C, dtype=torch.float32, device=xn.device)
-        dy_prev = torch.empty(B, C, dtype=torch.float32, device=xn.device) if (yp is not None and ctx.needs_input_grad[6]) else None
+        dy_prev = torch.empty(B, C, dtype=torch.float32, device=xn.device) if (yp is not None and ctx.needs_input_grad[7]) else None
         lib = hip_lib.load()
+        head = (ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(), _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second))
+        variant = (_p(yp), _p(dy_last), _p(dy_prev)) if ctx.carry else (_p(ctx.first),)
         if M == 1:
+            dx = torch.empty_like(xn)
+            dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
             ws = torch.empty(lib.vrwkv_ln_mix_ws_floats(ntok, C, M), dtype=torch.float32, device=xn.device)
-            rc = lib.vrwkv_ln_mix_bwd_carry_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
-                                                 _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), _p(d_xn), _p(yp), dy_last.data_ptr(),
-                                                 _p(dy_prev), dx.data_ptr(), dwb.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, "vrwkv_ln_mix_bwd_carry_bf16")
+            entry = "vrwkv_ln_mix_bwd_carry_bf16" if ctx.carry else "vrwkv_ln_mix_bwd_packed_bf16"
+            rc = getattr(lib, entry)(*head, _p(d_xn), *variant, dx.data_ptr(), dwb.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
+            hip_lib.check(rc, entry)
         else:       # six lerps: their backward with the LayerNorm output recomputed in place of a stored one, then the LayerNorm's
             dy = torch.empty_like(xn)
             ws = _ws(ntok, C, M, xn.device)
-            rc = lib.vrwkv_mix_bwd_ln_carry_bf16(ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(),
-                                                 _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second), _p(yp), dy_last.data_ptr(), _p(dy_prev),
-                                                 dy.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, "vrwkv_mix_bwd_ln_carry_bf16")
-            ws = torch.empty(lib.vrwkv_add_ln_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
-            rc = lib.vrwkv_add_ln_bwd_bf16(ntok, C, dy.data_ptr(), _p(d_xn), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                           wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, "vrwkv_add_ln_bwd_bf16")
-        dwb = dwb.to(wc.dtype)
-        dmu = dmu.to(xn.dtype)
-        return (dx, (dx if ctx.has_delta else None), dwb[0], dwb[1], None, None, dy_prev.to(ctx.prev_dtype) if dy_prev is not None else None,
-                *[dmu[i].view(sh) for i, sh in enumerate(ctx.mu_shapes)])
+            entry = "vrwkv_mix_bwd_ln_carry_bf16" if ctx.carry else "vrwkv_mix_bwd_ln_packed_bf16"
+            rc = getattr(lib, entry)(*head, *variant, dy.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
+            hip_lib.check(rc, entry)
+            dx, dwb = _add_ln_bwd(dy, d_xn, xn, mean, rstd, wc)
+        dwb, dmus = _param_grads(dwb, dmu, wc, xn, ctx.mu_shapes)
+        return (dx, (dx if ctx.has_delta else None), dwb[0], dwb[1], None, None, None, dy_prev.to(ctx.prev_dtype) if dy_prev is not None else None, None, *dmus)
 
 
 class RoutePlan:
@@ -848,18 +800,10 @@ class _AddLnMixRouted(torch.autograd.Function):
     def forward(ctx, x, delta, w_t, b_t, w_v, b_v, eps, plan, first, mu_t, mu_v):
         B, T, C = x.shape
         plan.check(B, T, x.device)
-        x = x.contiguous()
-        delta = delta.contiguous() if delta is not None else None
-        ws, bs = [w_t.contiguous(), w_v.contiguous()], [b_t.contiguous(), b_v.contiguous()]
-        mus = [mu_t.reshape(C).contiguous(), mu_v.reshape(C).contiguous()]
-        _chk(x, delta, *ws, *bs, *mus)
+        x, delta, params, xn, mean, rstd = _ln_fwd_pre("add_ln_mix_routed", x, delta, (w_t, w_v, b_t, b_v, mu_t, mu_v), first)
+        ws, bs, mus = params[0:2], params[2:4], params[4:6]
         ntok = B * T
-        xn = torch.empty_like(x) if delta is not None else x
         out = torch.empty(ntok, C, dtype=x.dtype, device=x.device)
-        mean = torch.empty(ntok, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(ntok, dtype=torch.float32, device=x.device)
-        if first is not None and (first.dtype != torch.uint8 or first.numel() != ntok or first.device != x.device or not first.is_contiguous()):
-            raise ValueError(f"add_ln_mix_routed: `first` must be a contiguous uint8 tensor of {ntok} marks on {x.device}")
         rc = hip_lib.load().vrwkv_ln_mix_routed_fwd_bf16(ntok, T, C, float(eps), x.data_ptr(), _p(delta), _ptr_array(ws), _ptr_array(bs), _ptr_array(mus),
                                                          xn.data_ptr() if delta is not None else 0, out.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                                          _p(first), plan.sel.data_ptr(), plan.pos.data_ptr(), 4, _stream(x))
@@ -893,10 +837,8 @@ class _AddLnMixRouted(torch.autograd.Function):
                                               _ptr_array([mu_t, mu_v]), dout.data_ptr(), _p(d_xn), _p(ctx.first), plan.sel.data_ptr(), plan.pos.data_ptr(), 4,
                                               dx.data_ptr(), dwb.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
         hip_lib.check(rc, "vrwkv_ln_mix_routed_bwd_bf16")
-        dwb = dwb.to(w_t.dtype)
-        dmu = dmu.to(xn.dtype)
-        return (dx, (dx if ctx.has_delta else None), dwb[0, 0], dwb[0, 1], dwb[1, 0], dwb[1, 1], None, None, None,
-                dmu[0].view(ctx.mu_shapes[0]), dmu[1].view(ctx.mu_shapes[1]))
+        dwb, dmus = _param_grads(dwb, dmu, w_t, xn, ctx.mu_shapes)
+        return (dx, (dx if ctx.has_delta else None), dwb[0, 0], dwb[0, 1], dwb[1, 0], dwb[1, 1], None, None, None, *dmus)
 
 
 def row_gather(src, idx):
@@ -949,34 +891,31 @@ def cmix_routed(block, x, att_out, plan, first=None, selective=False):
 def add_ln_mix(x, delta, ln, mus, dup3=False, first=None, carry=None):
     """Returns (x + delta, [lerp outputs]) -- see `_AddLnMix`.  first: the marks of a wkv7.PackedLayout (layout.first) for packed rows.
     carry: a 1-tuple (y_prev,) when x is one segment of a longer row (y_prev may be None: the row starts here); returns
-    (x + delta, [lerp outputs], y_last) then -- see `_AddLnMixCarry`."""
+    (x + delta, [lerp outputs], y_last) then."""
     if carry is not None:
         if first is not None:
             raise NotImplementedError("add_ln_mix: a carry together with packed rows")
-        xn, *outs, y_last = _AddLnMixCarry.apply(x, delta, ln.weight, ln.bias, ln.eps, dup3, carry[0], *mus)
+        xn, *outs, y_last = _AddLnMix.apply(x, delta, ln.weight, ln.bias, ln.eps, dup3, None, carry[0], True, *mus)
         return xn, outs, y_last
-    xn, *outs = _AddLnMix.apply(x, delta, ln.weight, ln.bias, ln.eps, dup3, first, *mus)
+    xn, *outs = _AddLnMix.apply(x, delta, ln.weight, ln.bias, ln.eps, dup3, first, None, False, *mus)
     return xn, outs
 
 
 def packed_supported(x):
     """May a packed batch (wkv7.PackedLayout) take blocks_forward?  It needs both shifts inside the ln_mix kernels: the two-kernel shift
-    (VRWKV_LN_MIX=0 / VRWKV_LN_MIX_TMIX=0, vrwkv_mix_fwd / _bwd) finds a first token as n % T == 0 only; the caller runs the unfused Blocks then."""
-    return ln_mix_supported(x) and LN_MIX_TMIX
+    (vrwkv_mix_fwd / _bwd, the path for C > 4096 and for input that is not 3-D) finds a first token as n % T == 0 only; the caller runs the
+    unfused Blocks then."""
+    return ln_mix_supported(x)
 
 
 def carry_supported(x):
     """May one segment of a cut row (rwkv7.TrainCarry) take blocks_forward?  As for packed rows, both shifts must be inside the ln_mix kernels;
     the caller runs the unfused Blocks otherwise."""
-    return ln_mix_supported(x) and LN_MIX_TMIX
-
-
-LN_MIX = os.environ.get("VRWKV_LN_MIX", "1") != "0"              # A/B switch: 0 = add_ln and mix as two kernels
-LN_MIX_TMIX = os.environ.get("VRWKV_LN_MIX_TMIX", "1") != "0"    # A/B switch: 0 = ln1 and the six time-mix lerps as two kernels
+    return ln_mix_supported(x)
 
 
 def ln_mix_supported(x):
-    return LN_MIX and add_ln_supported(x) and x.dim() == 3 and x.shape[-1] <= 4096
+    return add_ln_supported(x) and x.dim() == 3 and x.shape[-1] <= 4096
 
 
 def add_ln_supported(x):
@@ -999,7 +938,7 @@ def _block_segment(block, x, delta, v_first, selective=False, layout=None, carry
     if carry is not None:
         if layout is not None:
             raise NotImplementedError("a training carry together with packed rows")
-        if not (fuse and LN_MIX_TMIX):
+        if not fuse:
             raise NotImplementedError("a cut row needs the fused ln_mix kernels for both token shifts (fused.carry_supported)")
         dup3 = torch.is_grad_enabled() and GRAD_ALIAS and att.layer_id > 0
         x, mixed, att_x = add_ln_mix(x, delta, block.ln1, (att.x_r, att.x_w, att.x_k, att.x_v, att.x_a, att.x_g), dup3, None, (carry[0],))
@@ -1007,9 +946,9 @@ def _block_segment(block, x, delta, v_first, selective=False, layout=None, carry
         x, (k,), ffn_x = add_ln_mix(x, att_out, block.ln2, (ffn.x_k,), False, None, (carry[1],))
         return x, cmix_from_mixed(ffn, k, recompute_relusq=selective), v_first, att_x, ffn_x, s_end
     first = layout.first if layout is not None else None
-    if layout is not None and not (fuse and LN_MIX_TMIX):
+    if layout is not None and not fuse:
         raise NotImplementedError("packed rows need the fused ln_mix kernels for both token shifts (fused.packed_supported)")
-    if fuse and LN_MIX_TMIX:
+    if fuse:
         dup3 = torch.is_grad_enabled() and GRAD_ALIAS and att.layer_id > 0
         x, mixed = add_ln_mix(x, delta, block.ln1, (att.x_r, att.x_w, att.x_k, att.x_v, att.x_a, att.x_g), dup3, first)
         att_out, v_first = tmix_from_mixed(att, mixed, v_first, recompute_state=selective, layout=layout)

@@ -531,7 +531,7 @@ class RWKV(nn.Module):
                 return fused.blocks_forward(self, x, grad_cp=int(args.grad_cp) if torch.is_grad_enabled() else 0, layout=layout, **rk()), num_tokens_to_pad
         if layout is not None:
             # the unfused Blocks (masked shift in PyTorch, the WKV7 op packed on device tensors): CPU tensors, args.fused off, or the
-            # two-kernel shift selected (VRWKV_LN_MIX=0), whose kernels know no sample boundaries inside a row
+            # two-kernel shift's shapes (C > 4096), whose kernels know no sample boundaries inside a row
             v_first = torch.empty_like(x)
             for block in self.blocks:
                 if args.grad_cp >= 1 and torch.is_grad_enabled():
