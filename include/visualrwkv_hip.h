@@ -481,6 +481,25 @@ int vrwkv_ln_pool_scatter_fwd_bf16(int B, int T, int pad, int Lout, int C, float
 int vrwkv_ln_pool_gather_bwd_bf16(int B, int T, int pad, int Lout, int C, const void* dout, const long* row_index, const void* xn,
                                   const float* mean, const float* rstd, const void* w, void* dx, float* dwb, float* ws, void* stream);
 
+/* ---- RWKV vision encoder (VisualRWKV-v7/v7.10/src/model.py:367-415: VRWKV) --------------------------------------------------------- */
+/* VRWKV's tail in one pass each way: ln_out over every row (src/model.py:392), the masked scatter of ALL image tokens into the placeholder
+ * rows (preparing_embedding, :510-526) and the ImageNet head's mean over tokens (:393-394: head(x.mean(dim=1))).  x, delta: (B, L, C) bf16.
+ *   forward : xn = bf16(x + delta) (delta == NULL: xn = x, not written), statistics of the rounded xn;
+ *             out[row_index[b L + t]] = LayerNorm(xn[b, t]), vrwkv_ln_scatter_fwd_bf16's arithmetic bit for bit; row_index: device int64,
+ *             B L entries, distinct rows of `out`, a negative entry drops the row; NULL: out is (B L, C) in order.
+ *             pooled (B, C) bf16 = bf16(fma(mean_t xhat[b, t], w, b)), the sum in fp32 (the affine part commutes with the mean); a dropped
+ *             row still counts (the reference takes the mean before it truncates).  mean / rstd: B L fp32 each.
+ *   backward: g[b, t] = dout[row_index[b L + t]] (0 for a dropped row) + dpooled[b] / L in fp32; dout or dpooled may be NULL (not both);
+ *             dx (B, L, C) bf16 = vrwkv_add_ln_bwd_bf16's LayerNorm backward with g for dy; dwb (2 C fp32) = (dgamma, dbeta), written.
+ *             With dpooled == NULL: vrwkv_ln_gather_bwd_bf16 bit for bit.
+ * ws (both ways): vrwkv_ln_scatter_mean_ws_floats(B, L, C) floats (-1: unsupported shape).  Deterministic, no atomics.
+ * C % 64 == 0, C <= 8192 (VRWKV_ESHAPE otherwise). */
+long vrwkv_ln_scatter_mean_ws_floats(int B, int L, int C);
+int vrwkv_ln_scatter_mean_fwd_bf16(int B, int L, int C, float eps, const void* x, const void* delta, const void* w, const void* b,
+                                   const long* row_index, void* xn, void* out, void* pooled, float* mean, float* rstd, float* ws, void* stream);
+int vrwkv_ln_gather_mean_bwd_bf16(int B, int L, int C, const void* dout, const long* row_index, const void* dpooled, const void* xn,
+                                  const float* mean, const float* rstd, const void* w, void* dx, float* dwb, float* ws, void* stream);
+
 /* The same step with the clip factor formed on the device: sqnorm[0] = squared L2 norm of the (unscaled, summed over
  * ranks) gradient, grad scale = inv_world * min(1, clip / (sqrt(sqnorm) * inv_world + 1e-6)) (clip <= 0: no clipping).
  * Replaces Lightning's gradient_clip_val=1.0 host-side norm (train.py:92) without a device -> host synchronisation. */
@@ -516,6 +535,17 @@ int vrwkv_wgrad_skinny_bf16(long M, int Nw, int D, const void* wide, const void*
 long vrwkv_wgrad_big_ws_floats(long M, int N1, int N2);
 int vrwkv_wgrad_big_bf16(long M, int N1, int N2, const void* A, const void* B, void* out, float* ws, void* stream);
 
+
+/* ---- Weight gradient of a TRAINED patch embedding, Conv2d(3, N, 16, 16) with stride 16 (VisualRWKV-v7/v7.10/src/model.py:371,378:
+ * vrwkv.emb; autograd's convolution backward for the weight and the bias):
+ *   dW[n, (c P + py) P + px] = sum_{b,m} dout[b Mimg + m, n] pixels[b, c, gy P + py, gx P + px],  m = gy (Wimg / P) + gx;   dbias[n] = sum dout[., n]
+ * pixels (B,3,Himg,Wimg) bf16; dout (B Mimg, N) bf16 contiguous; dW (N, 3 P P) bf16; dbias (N) bf16 or NULL.  fp32 accumulation, one rounding,
+ * a fixed summation order (a second call is bit-identical), no atomics, and no unfolded copy of the images: csrc/patch_wgrad.h reads the
+ * patches from the pixels as they lie.  P == 16, Himg % 16 == 0, Wimg % 16 == 0, B Mimg % 32 == 0, N % 256 == 0, pixels below 4 GiB
+ * (VRWKV_ESHAPE otherwise).  ws: vrwkv_patch_embed_wgrad_ws_floats(...) floats, never 0 (-1: unsupported shape); all pointers 16-byte aligned. */
+long vrwkv_patch_embed_wgrad_ws_floats(int B, int Himg, int Wimg, int P, int N);
+int vrwkv_patch_embed_wgrad_bf16(int B, int Himg, int Wimg, int P, int N, const void* pixels, const void* dout, void* dW, void* dbias,
+                                 float* ws, void* stream);
 
 /* Streaming copy dst = src (bytes % 16 == 0): the on-box copy ceiling the WKV roofline fraction is also reported
  * against.  Moves 2 * bytes of HBM traffic. */

@@ -236,6 +236,45 @@ int vrwkv_ln_pool_gather_bwd_bf16(int B, int T, int pad, int Lout, int C, const 
     return done();
 }
 
+// The RWKV vision encoder's tail: ln_out over all rows scattered into the placeholder rows, and the ImageNet head's mean over tokens of the same
+// rows, one read of the residual stream each way (VisualRWKV-v7/v7.10/src/model.py:392-394,510-526); see ln_scatter_mean_fwd_kernel.
+// ws (both ways): vrwkv_ln_scatter_mean_ws_floats(B, L, C) floats -- the forward's per-range partial sums / the backward's (dgamma, dbeta) rows.
+constexpr int LN_MEAN_ROWS = 8, LN_MEAN_PARTS = 64;         // rows a forward workgroup walks, and the cap on partial rows per sample
+inline int ln_mean_parts(int L) { const int p = (L + LN_MEAN_ROWS - 1) / LN_MEAN_ROWS; return p < LN_MEAN_PARTS ? p : LN_MEAN_PARTS; }
+
+long vrwkv_ln_scatter_mean_ws_floats(int B, int L, int C) {
+    if (B <= 0 || L <= 0 || !ln_ok(C) || (long)B * ln_mean_parts(L) >= (1L << 31)) return -1;
+    const long f = (long)B * ln_mean_parts(L) * C, bw = vrwkv_add_ln_ws_floats((long)B * L, C);
+    return f > bw ? f : bw;
+}
+
+int vrwkv_ln_scatter_mean_fwd_bf16(int B, int L, int C, float eps, const void* x, const void* delta, const void* w, const void* b,
+                                   const long* row_index, void* xn, void* out, void* pooled, float* mean, float* rstd, float* ws, void* stream) {
+    if (B <= 0 || L <= 0 || !x || !w || !b || !out || !pooled || !mean || !rstd || !ws || (delta && !xn)) return VRWKV_EINVAL;
+    if (!ln_ok(C) || (long)B * ln_mean_parts(L) >= (1L << 31)) return VRWKV_ESHAPE;
+    const int P = ln_mean_parts(L);
+    hipLaunchKernelGGL(ln_scatter_mean_fwd_kernel, dim3((unsigned)(B * P)), dim3(ln_threads(C)), 0, (hipStream_t)stream, L, P, C, eps, (const uint16_t*)x,
+                       (const uint16_t*)delta, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, (uint16_t*)out, mean, rstd, row_index, ws);
+    const long n = (long)B * C;
+    hipLaunchKernelGGL(ln_mean_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, P, C, 1.f / (float)L, ws,
+                       (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)pooled);
+    return done();
+}
+
+// dout (rows of the scattered tensor) and dpooled (B, C) bf16: either may be NULL, not both; row_index NULL: dout is (B L, C) in order.
+// dx (B, L, C) bf16, dwb (2 C fp32) = (dgamma, dbeta), written.  With dpooled == NULL this is vrwkv_ln_gather_bwd_bf16 bit for bit.
+int vrwkv_ln_gather_mean_bwd_bf16(int B, int L, int C, const void* dout, const long* row_index, const void* dpooled, const void* xn,
+                                  const float* mean, const float* rstd, const void* w, void* dx, float* dwb, float* ws, void* stream) {
+    if (B <= 0 || L <= 0 || (!dout && !dpooled) || !xn || !mean || !rstd || !w || !dx || !dwb || !ws) return VRWKV_EINVAL;
+    if (!ln_ok(C)) return VRWKV_ESHAPE;
+    const long ntok = (long)B * L;
+    const int G = ln_bwd_grid(ntok);
+    hipLaunchKernelGGL(ln_gather_mean_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, L, C, (const uint16_t*)dout, row_index,
+                       (const uint16_t*)dpooled, (const uint16_t*)xn, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws);
+    colsum(G, 2L * C, ws, dwb, (hipStream_t)stream);
+    return done();
+}
+
 int vrwkv_add_ln_bwd_bf16(long ntok, int C, const void* dy, const void* dres, const void* xn, const float* mean,
                           const float* rstd, const void* w, void* dx, float* dwb, float* ws, void* stream) {
     if (ntok <= 0 || !dy || !xn || !mean || !rstd || !w || !dx || !dwb || !ws) return VRWKV_EINVAL;

@@ -916,6 +916,157 @@ __global__ __launch_bounds__(1024) void ln_pool_bwd_kernel(int B, int T, int pad
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// The RWKV vision encoder's tail (VisualRWKV-v7/v7.10/src/model.py:392-394 ln_out and the ImageNet head's mean over tokens, :510-526 the masked
+// scatter): (B, L, C) rows, every row is normalised once and leaves twice --
+//   out[orow[b L + t]] = bf16(fma(xhat, w, b))  (add_ln_fwd_kernel's row, bit for bit),   pooled[b] = bf16(fma(sum_t xhat[b, t] / L, w, b))
+// with xhat = (xn - mean) rstd, xn = bf16(x + delta): the affine part commutes with the mean (ln_pool_fwd_kernel's convention).  A dropped row
+// (orow < 0) still counts in the mean.  Workgroup (b, p) of B P walks rows [L p / P, L (p + 1) / P) of sample b with the next row in flight and
+// leaves one fp32 partial row of the sum; ln_mean_finish_kernel adds the P partial rows of a sample in order: deterministic, no atomics.
+__global__ __launch_bounds__(1024) void ln_scatter_mean_fwd_kernel(int L, int P, int C, float eps, const uint16_t* __restrict__ x,
+                                                                   const uint16_t* __restrict__ delta, const uint16_t* __restrict__ w,
+                                                                   const uint16_t* __restrict__ b, uint16_t* __restrict__ xn, uint16_t* __restrict__ out,
+                                                                   float* __restrict__ mean, float* __restrict__ rstd, const long* __restrict__ orow,
+                                                                   float* __restrict__ part) {
+    __shared__ float red[4][MAXW][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int c0 = threadIdx.x * 8;
+    const bool act = c0 < C;
+    const long bi = blockIdx.x / P;
+    const int pi = (int)(blockIdx.x - bi * P);
+    const long lo = bi * L + (long)L * pi / P, hi = bi * L + (long)L * (pi + 1) / P;
+    const uint4 z4 = make_uint4(0, 0, 0, 0);
+    const V8 wv = unpack8(act ? ldg(w + c0) : z4), bv = unpack8(act ? ldg(b + c0) : z4);
+    const float inv_c = 1.f / (float)C;
+    V8 acc;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc.f[e] = 0.f;
+    uint4 nx = z4, nd = z4;
+    if (lo < hi && act) { nx = ldg(x + lo * C + c0); if (delta) nd = ldg(delta + lo * C + c0); }
+    for (long n = lo; n < hi; ++n) {
+        const uint4 cx = nx, cd = nd;
+        if (n + 1 < hi && act) {
+            nx = ldg(x + (n + 1) * C + c0);
+            if (delta) nd = ldg(delta + (n + 1) * C + c0);
+        }
+        V8 v = unpack8(cx);
+        if (delta) {
+            const V8 d = unpack8(cd);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v.f[e] += d.f[e];
+            const uint4 r = pack8(v);
+            if (act) stg(xn + n * C + c0, r);
+            v = unpack8(r);
+        }
+        const int par = (int)(n & 1) * 2;
+        float s[1] = {0.f};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[0] += v.f[e];
+        block_sum<1>(red, par, wave, lane, nw, s);
+        const float mu = s[0] * inv_c;
+        float q[1] = {0.f};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float t = act ? v.f[e] - mu : 0.f; q[0] = fmaf(t, t, q[0]); }
+        block_sum<1>(red, par + 1, wave, lane, nw, q);
+        const float rs = rsqrtf(q[0] * inv_c + eps);
+        V8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float xh = (v.f[e] - mu) * rs;
+            acc.f[e] += xh;
+            o.f[e] = fmaf(xh, wv.f[e], bv.f[e]);
+        }
+        const long orow_n = orow ? orow[n] : n;                 // a negative row is dropped
+        if (act && orow_n >= 0) stg(out + orow_n * C + c0, pack8(o));
+        if (threadIdx.x == 0) { mean[n] = mu; rstd[n] = rs; }
+    }
+    if (act) {
+        float* dst = part + (size_t)blockIdx.x * C + c0;
+        *reinterpret_cast<float4*>(dst) = make_float4(acc.f[0], acc.f[1], acc.f[2], acc.f[3]);
+        *reinterpret_cast<float4*>(dst + 4) = make_float4(acc.f[4], acc.f[5], acc.f[6], acc.f[7]);
+    }
+}
+
+// pooled[b, c] = bf16(fma(sum_p part[b, p, c] / L, w[c], b[c])); one thread per element
+__global__ __launch_bounds__(256) void ln_mean_finish_kernel(long n, int P, int C, float inv_l, const float* __restrict__ part, const uint16_t* __restrict__ w,
+                                                             const uint16_t* __restrict__ b, uint16_t* __restrict__ pooled) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long bi = i / C;
+    const int c = (int)(i - bi * C);
+    const float* src = part + (size_t)bi * P * C + c;
+    float t = src[0];
+    for (int p = 1; p < P; ++p) t += src[(size_t)p * C];
+    pooled[i] = (uint16_t)f32_to_bf16_bits(fmaf(t * inv_l, bf16_to_f32(w[c]), bf16_to_f32(b[c])));
+}
+
+// ... and its backward: row (b, t) collects g = dout[orow[b L + t]] (0 for a dropped row, or without dout) + dpooled[b] / L (fp32; without dpooled g is
+// dout's row itself), then add_ln_bwd_kernel's row with g for dy and no residual gradient.  Same ranges, partial rows and prefetch as that kernel.
+__global__ __launch_bounds__(1024) void ln_gather_mean_bwd_kernel(long ntok, int L, int C, const uint16_t* __restrict__ dout, const long* __restrict__ orow,
+                                                                  const uint16_t* __restrict__ dpooled, const uint16_t* __restrict__ xn,
+                                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                  const uint16_t* __restrict__ w, uint16_t* __restrict__ dx, float* __restrict__ part) {
+    __shared__ float red[2][MAXW][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int c0 = threadIdx.x * 8;
+    const bool act = c0 < C;
+    const long lo = ntok * blockIdx.x / gridDim.x, hi = ntok * (blockIdx.x + 1) / gridDim.x;
+    const uint4 z4 = make_uint4(0, 0, 0, 0);
+    const V8 wv = unpack8(act ? ldg(w + c0) : z4);
+    const float inv_c = 1.f / (float)C, inv_l = 1.f / (float)L;
+    V8 gw, gb;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { gw.f[e] = 0.f; gb.f[e] = 0.f; }
+    struct Row { uint4 y, p, x; float mu, rs; };
+    auto fetch = [&](long n) {
+        Row r{z4, z4, z4, 0.f, 0.f};
+        if (act) {
+            if (dout) { const long o = orow ? orow[n] : n; if (o >= 0) r.y = ldg(dout + o * C + c0); }
+            if (dpooled) r.p = *reinterpret_cast<const uint4*>(dpooled + (n / L) * C + c0);      // L rows share it: cached
+            r.x = ldg(xn + n * C + c0);
+        }
+        r.mu = mean[n]; r.rs = rstd[n];
+        return r;
+    };
+    Row nxt{z4, z4, z4, 0.f, 0.f};
+    if (lo < hi) nxt = fetch(lo);
+    for (long n = lo; n < hi; ++n) {
+        const Row cur = nxt;
+        if (n + 1 < hi) nxt = fetch(n + 1);
+        V8 d = unpack8(cur.y);
+        if (dpooled) {
+            const V8 dp = unpack8(cur.p);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) d.f[e] = fmaf(dp.f[e], inv_l, d.f[e]);
+        }
+        const V8 xv = unpack8(cur.x);
+        V8 xh, g;
+        float s[2] = {0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            xh.f[e] = act ? (xv.f[e] - cur.mu) * cur.rs : 0.f;
+            g.f[e] = d.f[e] * wv.f[e];
+            s[0] += g.f[e];
+            s[1] = fmaf(g.f[e], xh.f[e], s[1]);
+            gw.f[e] = fmaf(d.f[e], xh.f[e], gw.f[e]);
+            gb.f[e] += d.f[e];
+        }
+        block_sum<2>(red, (int)(n & 1), wave, lane, nw, s);
+        const float c1 = s[0] * inv_c, c2 = s[1] * inv_c;
+        V8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o.f[e] = fmaf(cur.rs, g.f[e] - c1 - xh.f[e] * c2, 0.f);
+        if (act) stg(dx + n * C + c0, pack8(o));
+    }
+    if (act) {
+        float* dst = part + (size_t)blockIdx.x * 2 * C + c0;
+        *reinterpret_cast<float4*>(dst) = make_float4(gw.f[0], gw.f[1], gw.f[2], gw.f[3]);
+        *reinterpret_cast<float4*>(dst + 4) = make_float4(gw.f[4], gw.f[5], gw.f[6], gw.f[7]);
+        *reinterpret_cast<float4*>(dst + C) = make_float4(gb.f[0], gb.f[1], gb.f[2], gb.f[3]);
+        *reinterpret_cast<float4*>(dst + C + 4) = make_float4(gb.f[4], gb.f[5], gb.f[6], gb.f[7]);
+    }
+}
+
 // dst[i] = src[idx[i]] on rows of C bf16 (cv = C / 8 16-byte pieces per row; idx int32, or int64 with IDX64): the routed channel mix's way back to
 // token order, and with the inverse index that step's backward
 template <bool IDX64>

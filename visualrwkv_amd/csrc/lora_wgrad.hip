@@ -4,6 +4,7 @@
 #include "../../include/visualrwkv_hip.h"
 #include <lora_wgrad.h>
 #include <wgrad_big.h>
+#include <patch_wgrad.h>
 
 namespace {
 
@@ -91,6 +92,61 @@ extern "C" int vrwkv_wgrad_big_bf16(long M, int N1, int N2, const void* A, const
     if (S > 1) {
         const long n = (long)N1 * N2;
         hipLaunchKernelGGL(wgb::wgrad_big_reduce, dim3((unsigned)((n / 4 + 255) / 256 > 8192 ? 8192 : (n / 4 + 255) / 256)), dim3(256), 0, st, ws, S, n, (uint16_t*)out);
+        e = hipGetLastError();
+    }
+    return e == hipSuccess ? VRWKV_OK : (int)e;
+}
+
+// ---- weight gradient of a trained patch embedding (patch_wgrad.h): dW (N x 768) = dout^T patches(pixels), dbias = column sums
+namespace {
+constexpr int PATCH_P = 16, PATCH_K = 3 * PATCH_P * PATCH_P;       // 768 = three tile columns, one per colour channel
+constexpr int BIAS_SLICES = 64;                                    // row slices of the dbias partial sums
+inline int bias_slices(long M) { return (int)(M / wgb::KT < BIAS_SLICES ? M / wgb::KT : BIAS_SLICES); }
+inline bool patch_shape_ok(int B, int Himg, int Wimg, int P, int N) {
+    if (B <= 0 || Himg <= 0 || Wimg <= 0 || N <= 0) return false;
+    if (P != PATCH_P || Himg % PATCH_P != 0 || Wimg % PATCH_P != 0 || N % wgb::TM != 0) return false;
+    const long M = (long)B * (Himg / PATCH_P) * (Wimg / PATCH_P);
+    if (M % wgb::KT != 0 || M >= (1L << 31)) return false;
+    return (long)B * 3 * Himg * Wimg * 2 < (1L << 32);             // the kernel's pixel byte offsets are 32-bit
+}
+}  // namespace
+
+extern "C" long vrwkv_patch_embed_wgrad_ws_floats(int B, int Himg, int Wimg, int P, int N) {
+    if (!patch_shape_ok(B, Himg, Wimg, P, N)) return -1;
+    const long M = (long)B * (Himg / PATCH_P) * (Wimg / PATCH_P);
+    const int S = big_splits(M, N, PATCH_K);
+    return (S > 1 ? (long)S * N * PATCH_K : 0) + (long)bias_slices(M) * N;
+}
+
+extern "C" int vrwkv_patch_embed_wgrad_bf16(int B, int Himg, int Wimg, int P, int N, const void* pixels, const void* dout, void* dW,
+                                            void* dbias, float* ws, void* stream) {
+    if (B <= 0 || Himg <= 0 || Wimg <= 0 || N <= 0 || !pixels || !dout || !dW || !ws) return VRWKV_EINVAL;
+    if (!patch_shape_ok(B, Himg, Wimg, P, N)) return VRWKV_ESHAPE;
+    if ((reinterpret_cast<uintptr_t>(pixels) | reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dW) | reinterpret_cast<uintptr_t>(ws)) & 15u)
+        return VRWKV_EALIGN;
+    const int gw = Wimg / PATCH_P, Mimg = (Himg / PATCH_P) * gw;
+    const long M = (long)B * Mimg;
+    const int S = big_splits(M, N, PATCH_K);
+    const hipStream_t st = (hipStream_t)stream;
+    const wgp::Args a{M, N, PATCH_K, S, (const uint16_t*)dout, (const uint16_t*)pixels, ws, (uint16_t*)dW, Mimg, gw, Himg, Wimg,
+                      wgp::Div::make((unsigned)Mimg), wgp::Div::make((unsigned)gw)};
+    const size_t lds = (size_t)wgb::STAGES * 2 * wgb::OPB;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgp::wgrad_patch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(wgp::wgrad_patch_kernel, dim3((unsigned)((N / wgb::TM) * 3 * S)), dim3(512), lds, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    const long n = (long)N * PATCH_K;
+    if (S > 1) {
+        hipLaunchKernelGGL(wgb::wgrad_big_reduce, dim3((unsigned)((n / 4 + 255) / 256 > 8192 ? 8192 : (n / 4 + 255) / 256)), dim3(256), 0, st, ws, S, n, (uint16_t*)dW);
+        e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    if (dbias) {
+        float* part = ws + (S > 1 ? (size_t)S * n : 0);
+        const int G = bias_slices(M);
+        hipLaunchKernelGGL(wgp::colsum_part_kernel, dim3((unsigned)(N / 256), (unsigned)G), dim3(256), 0, st, M, N, (const uint16_t*)dout, part);
+        hipLaunchKernelGGL(wgp::colsum_finish_kernel, dim3((unsigned)(N / 256)), dim3(256), 0, st, G, N, part, (uint16_t*)dbias);
         e = hipGetLastError();
     }
     return e == hipSuccess ? VRWKV_OK : (int)e;

@@ -130,12 +130,20 @@ def build_sample(sample: Dict, tokenizer, ctx_len: int, num_token_per_image: int
 
 
 def multi_image_collate_fn(batch: Sequence[Dict]) -> Dict:
-    """dataset.py:23-36: stack ids/labels, concatenate every tower's images over the samples that have any."""
+    """dataset.py:23-36: stack ids/labels, concatenate every tower's images over the samples that have any.
+    v7.10 (its dataset.py:25-39): a sample's `images` may be ONE tensor (n, 3, H, W) for the RWKV vision encoder -- collated to
+    {"image", "num_image_per_sample"} -- and the batch carries `cls_labels` (int64 (B,)) when its first sample has one."""
     with_img = [x for x in batch if "images" in x]
-    images = {k: torch.cat([x["images"][k] for x in with_img], dim=0) for k in ("dino", "sam", "siglip")}
-    images["num_image_per_sample"] = [len(x["images"]["dino"]) for x in with_img]
-    return dict(input_text=[x["input_text"] for x in batch], input_ids=torch.stack([x["input_ids"] for x in batch]),
-                labels=torch.stack([x["labels"] for x in batch]), images=images, sample_id=[str(x["sample_id"]) for x in batch])
+    if with_img and torch.is_tensor(with_img[0]["images"]):
+        images = {"image": torch.cat([x["images"] for x in with_img], dim=0), "num_image_per_sample": [len(x["images"]) for x in with_img]}
+    else:
+        images = {k: torch.cat([x["images"][k] for x in with_img], dim=0) for k in ("dino", "sam", "siglip")}
+        images["num_image_per_sample"] = [len(x["images"]["dino"]) for x in with_img]
+    out = dict(input_text=[x["input_text"] for x in batch], input_ids=torch.stack([x["input_ids"] for x in batch]),
+               labels=torch.stack([x["labels"] for x in batch]), images=images, sample_id=[str(x["sample_id"]) for x in batch])
+    if batch[0].get("cls_labels") is not None:
+        out["cls_labels"] = torch.stack([torch.as_tensor(x["cls_labels"], dtype=torch.long) for x in batch])
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------

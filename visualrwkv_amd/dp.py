@@ -92,10 +92,11 @@ class Zero1Engine:
         # reverse registration order for the language model (head, blocks N-1 .. 0), and whatever feeds the language model's
         # INPUT (the image projector `proj`, the visual token compressor `vtc` behind it, the embedding) last -- their gradients only exist
         # when the backward has walked the whole stack; among them reverse registration order again: vtc (ln_out, Blocks n-1 .. 0), proj, emb.
+        # The RWKV vision encoder `vrwkv` (v7.10) feeds the input the same way: vrwkv (head, ln_out, Blocks n-1 .. 0, emb), then rwkv.emb.
         # (Plain reverse registration order put `proj`, which is registered last, at the front of bucket 0 and kept that bucket from being
         # reduced until the very end of the backward; `vtc`, registered after it, would sit there the same way.)
         names = {id(p): n for n, p in model.named_parameters()}
-        late = lambda p: names.get(id(p), "").startswith(("proj.", "vtc.", "rwkv.emb.", "emb."))
+        late = lambda p: names.get(id(p), "").startswith(("proj.", "vtc.", "vrwkv.", "rwkv.emb.", "emb."))
         by_ready = [p for p in params[::-1] if not late(p)] + [p for p in params[::-1] if late(p)]
         # as VisualRWKV.optimizer_groups: at least 2-D after squeeze() = weight decay, except the learnable initial WKV states (args.state_tune)
         decays = lambda p: len(p.squeeze().shape) >= 2 and not names.get(id(p), "").endswith(".time_state")

@@ -989,6 +989,17 @@ def blocks_forward(rwkv, x, grad_cp=0, layout=None, carry=None, route=None):
     with the carry tensors among its arguments, mode 2 lets the WKV7 state op regenerate its by-products from the carried state) and the
     result is (hidden, the carry leaving the segment).
     route: a RoutePlan when the Blocks have `ffn_v` (args.modality_ffn); every mode passes it to every Block.  Not together with a carry."""
+    x, delta, layers = _blocks_walk(rwkv, x, grad_cp, layout, carry, route)
+    _, h = add_ln(x, delta, rwkv.ln_out)
+    if carry is not None:
+        from .rwkv7 import TrainCarry
+        return h, TrainCarry(len(layers), layers)
+    return h
+
+
+def _blocks_walk(rwkv, x, grad_cp=0, layout=None, carry=None, route=None):
+    """blocks_forward up to (not including) ln_out, on any module with `blocks` (Block 0 owns ln0): returns (x, pending delta, the per-layer
+    carries leaving the segment), so that a caller can fold the last residual add into its own tail kernel (vrwkv_forward)."""
     grad_cp = int(grad_cp) if torch.is_grad_enabled() else 0
     if grad_cp not in (0, 1, 2):
         raise ValueError(f"grad_cp = {grad_cp}: 0 (keep everything), 1 (re-compute every block, the reference's recipe) or 2 (selective recompute)")
@@ -1015,11 +1026,7 @@ def blocks_forward(rwkv, x, grad_cp=0, layout=None, carry=None, route=None):
             x, delta, v_first = checkpoint(_block_segment, block, x, delta, v_first, False, layout, None, route, use_reentrant=False)
         else:
             x, delta, v_first = _block_segment(block, x, delta, v_first, grad_cp == 2, layout, None, route)
-    _, h = add_ln(x, delta, rwkv.ln_out)
-    if carry is not None:
-        from .rwkv7 import TrainCarry
-        return h, TrainCarry(len(layers), layers)
-    return h
+    return x, delta, layers
 
 
 class _FusedCE(torch.autograd.Function):
@@ -1841,3 +1848,161 @@ def patch_embed(x, weight, bias, pos=None, prefix=None, padded_weight=None):
                                                hip_lib.launch_stream(x.device))
     hip_lib.check(rc, "vrwkv_patch_embed_bf16")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# The trainable RWKV vision encoder of VisualRWKV-v7/v7.10 (src/model.py:367-415: VRWKV): patch embedding with a weight gradient
+# (csrc/patch_wgrad.h), plain Blocks, and the tail ln_out + scatter + mean over tokens (csrc/ln_kernels.h: ln_scatter_mean_*)
+# ------------------------------------------------------------------------------------------------
+PATCH_WGRAD = os.environ.get("VRWKV_PATCH_WGRAD", "1") != "0"     # A/B switch: 0 = F.unfold + the library's GEMM for the weight gradient
+VRWKV_TAIL = os.environ.get("VRWKV_TAIL", "1") != "0"             # A/B switch: 0 = add_ln, index_copy and mean for the tail
+
+
+def patch_wgrad_supported(x, weight):
+    """May the weight gradient of a patch embedding run as vrwkv_patch_embed_wgrad_bf16?  P = 16 (P = 14: 28-byte pixel segments cannot be moved by
+    LDS-DMA), N % 256 == 0, B Mimg % 32 == 0, images below 4 GiB."""
+    if not (visual_supported(x) and x.dim() == 4 and x.shape[1] == 3 and weight.dim() == 4 and weight.dtype == torch.bfloat16):
+        return False
+    B, _, H, W = x.shape
+    N, patch = weight.shape[0], weight.shape[-1]
+    return hip_lib.load().vrwkv_patch_embed_wgrad_ws_floats(B, H, W, patch, N) > 0
+
+
+class _PatchEmbedTrain(torch.autograd.Function):
+    """conv2d(x, weight, bias, stride=patch).flatten(2).transpose(1, 2) with a trained weight: the forward is patch_embed's kernel (for P = 16 the
+    weight viewed as (N, 768) is already what it reads: no copy), the backward vrwkv_patch_embed_wgrad_bf16 straight from the pixels -- or, for
+    shapes that kernel refuses (P = 14, N % 256 != 0), F.unfold and a GEMM.  There is no pixel gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        if x.requires_grad:
+            raise ValueError("patch_embed_train: no gradient flows to the pixels")
+        N, patch = weight.shape[0], weight.shape[-1]
+        x = x.contiguous()
+        wc = weight.contiguous()
+        K = wc[0].numel()
+        wp = wc.view(N, K) if hip_lib.load().vrwkv_patch_embed_kp(patch) == K else padded_patch_weight(wc)
+        out = patch_embed(x, wc, bias, None, None, padded_weight=wp)
+        ctx.save_for_backward(x)
+        ctx.wshape, ctx.has_bias, ctx.kernel = tuple(weight.shape), bias is not None, PATCH_WGRAD and patch_wgrad_supported(x, wc)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, = ctx.saved_tensors
+        B, _, H, W = x.shape
+        N, _, patch, _ = ctx.wshape
+        d2 = dout.contiguous().view(-1, N)
+        if not ctx.kernel:
+            cols = F.unfold(x, patch, stride=patch).transpose(1, 2).reshape(d2.shape[0], -1)
+            dw = wgrad_big(d2, cols) if wgrad_big_supported(d2, cols) else d2.t() @ cols
+            return None, dw.view(ctx.wshape), (d2.sum(0, dtype=torch.float32).to(d2.dtype) if ctx.has_bias else None)
+        lib = hip_lib.load()
+        dw = torch.empty(ctx.wshape, dtype=torch.bfloat16, device=x.device)
+        db = torch.empty(N, dtype=torch.bfloat16, device=x.device) if ctx.has_bias else None
+        ws = torch.empty(lib.vrwkv_patch_embed_wgrad_ws_floats(B, H, W, patch, N), dtype=torch.float32, device=x.device)
+        rc = lib.vrwkv_patch_embed_wgrad_bf16(B, H, W, patch, N, x.data_ptr(), d2.data_ptr(), dw.data_ptr(), _p(db), ws.data_ptr(), _stream(x))
+        hip_lib.check(rc, "vrwkv_patch_embed_wgrad_bf16")
+        return None, dw, db
+
+
+def patch_embed_train(x, weight, bias):
+    """See `_PatchEmbedTrain`: (B, 3, H, W) bf16 pixels -> (B, tokens, N) with gradients for weight and bias."""
+    return _PatchEmbedTrain.apply(x, weight, bias)
+
+
+class _LnScatterMean(torch.autograd.Function):
+    """VRWKV's tail: LayerNorm(x + delta) of (B, L, C); row b L + t is written to row row_index[b L + t] of `embeds` (rows, C), which is modified in
+    place and returned (a negative row is dropped), and pooled (B, C) = the mean over tokens of the same normalised rows (dropped rows included).
+    embeds = None: a new dense (B L, C) tensor in order (row_index must be None too).  embeds must not be a view of another tensor: autograd
+    refuses an op with two outputs that writes into one."""
+
+    @staticmethod
+    def forward(ctx, embeds, x, delta, w, b, row_index, eps):
+        B, L, C = x.shape
+        x = x.contiguous()
+        delta = delta.contiguous() if delta is not None else None
+        wc, bc = w.contiguous(), b.contiguous()
+        _chk(embeds, x, delta, wc, bc)
+        if (embeds is None) != (row_index is None):
+            raise ValueError("ln_scatter_mean: `embeds` and `row_index` go together")
+        if row_index is not None and (row_index.dtype != torch.int64 or row_index.numel() != B * L or row_index.device != x.device
+                                      or not row_index.is_contiguous()):
+            raise ValueError(f"ln_scatter_mean: row_index must hold {B * L} contiguous int64 rows on {x.device}")
+        if embeds is not None and (embeds.dim() != 2 or embeds.shape[1] != C or not embeds.is_contiguous()):
+            raise ValueError("ln_scatter_mean: embeds must be a contiguous (rows, C) tensor")
+        lib = hip_lib.load()
+        out = embeds if embeds is not None else torch.empty(B * L, C, dtype=x.dtype, device=x.device)
+        pooled = torch.empty(B, C, dtype=x.dtype, device=x.device)
+        xn = torch.empty_like(x) if delta is not None else x
+        mean = torch.empty(B * L, dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        ws = torch.empty(lib.vrwkv_ln_scatter_mean_ws_floats(B, L, C), dtype=torch.float32, device=x.device)
+        rc = lib.vrwkv_ln_scatter_mean_fwd_bf16(B, L, C, float(eps), x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(), _p(row_index),
+                                                xn.data_ptr() if delta is not None else 0, out.data_ptr(), pooled.data_ptr(), mean.data_ptr(),
+                                                rstd.data_ptr(), ws.data_ptr(), _stream(x))
+        hip_lib.check(rc, "vrwkv_ln_scatter_mean_fwd_bf16")
+        if embeds is not None:
+            ctx.mark_dirty(embeds)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xn, mean, rstd, wc, row_index)
+        ctx.has_delta, ctx.scatter = delta is not None, embeds is not None
+        return out, pooled
+
+    @staticmethod
+    def backward(ctx, dout, dpooled):
+        xn, mean, rstd, wc, row_index = ctx.saved_tensors
+        B, L, C = xn.shape
+        if dout is None and dpooled is None:
+            return (None,) * 7
+        dout = dout.contiguous() if dout is not None else None
+        dpooled = dpooled.contiguous() if dpooled is not None else None
+        _chk(dout, dpooled)
+        lib = hip_lib.load()
+        dx = torch.empty_like(xn)
+        dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
+        ws = torch.empty(lib.vrwkv_ln_scatter_mean_ws_floats(B, L, C), dtype=torch.float32, device=xn.device)
+        rc = lib.vrwkv_ln_gather_mean_bwd_bf16(B, L, C, _p(dout), _p(row_index), _p(dpooled), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                               wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
+        hip_lib.check(rc, "vrwkv_ln_gather_mean_bwd_bf16")
+        d_emb = None
+        if ctx.scatter and ctx.needs_input_grad[0] and dout is not None:    # as _LnScatter: rows that were overwritten do not reach the embedding
+            R = dout.shape[0]
+            d_emb = torch.empty(R + 1, C, dtype=dout.dtype, device=dout.device)
+            d_emb[:R] = dout
+            d_emb.index_fill_(0, torch.where(row_index < 0, R, row_index), 0)
+            d_emb = d_emb[:R]
+        return d_emb, dx, (dx if ctx.has_delta else None), dwb[0].to(wc.dtype), dwb[1].to(wc.dtype), None, None
+
+
+def ln_scatter_mean(x, delta, ln, embeds2d=None, row_index=None):
+    """See `_LnScatterMean`; returns (embeds2d modified in place -- or the dense (B L, C) rows when it is None --, pooled (B, C))."""
+    return _LnScatterMean.apply(embeds2d, x, delta, ln.weight, ln.bias, row_index, ln.eps)
+
+
+def vrwkv_supported(vrwkv, images):
+    """May a rwkv7.VRWKV take vrwkv_forward?  bf16 pixels on the GPU with args.fused, a patch embedding the forward kernel accepts, rows the
+    LayerNorm kernels accept."""
+    w = vrwkv.emb.weight
+    return (bool(getattr(vrwkv.args, "fused", False)) and images.dim() == 4 and w.dtype == torch.bfloat16 and vrwkv.ln_out.weight.dtype == torch.bfloat16
+            and patch_embed_supported(images, w.shape[-1], w.shape[0]) and w.shape[0] % 64 == 0 and w.shape[0] <= 8192 and len(vrwkv.blocks) > 0)
+
+
+def vrwkv_forward(vrwkv, images, embeds2d=None, row_index=None, grad_cp=0):
+    """rwkv7.VRWKV.forward on the fused path (src/model.py:376-395): patch embedding -> Blocks on the (x, pending delta) stream -> the tail kernel,
+    which applies ln_out to every token, writes it into rows `row_index` of embeds2d (or a dense (B, L, C) tensor) and forms the mean over tokens
+    for the ImageNet head.  Returns (embeds2d modified in place, or the features (B, L, C); logits (B, 1000))."""
+    x = patch_embed_train(images, vrwkv.emb.weight, vrwkv.emb.bias)
+    B, L, C = x.shape
+    if L % 16 != 0:
+        raise ValueError(f"vrwkv_forward: {L} tokens per image must be a multiple of 16")
+    x, delta, _ = _blocks_walk(vrwkv, x, grad_cp)
+    if not VRWKV_TAIL:                              # the composite of what existed before the tail kernels
+        _, h = add_ln(x, delta, vrwkv.ln_out)
+        logits = vrwkv.head(h.mean(dim=1))
+        if embeds2d is None:
+            return h, logits
+        keep = row_index >= 0
+        return embeds2d.index_copy(0, row_index[keep], h.reshape(B * L, C)[keep]), logits
+    out, pooled = ln_scatter_mean(x, delta, vrwkv.ln_out, embeds2d, row_index)
+    return (out if embeds2d is not None else out.view(B, L, C)), vrwkv.head(pooled)

@@ -98,6 +98,9 @@ PROTOTYPES = {
     "vrwkv_flip_add_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 4),
     "vrwkv_ln_pool_scatter_fwd_bf16": (_c_int, [_c_int] * 5 + [_c_float] + [_c_void_p] * 10),
     "vrwkv_ln_pool_gather_bwd_bf16": (_c_int, [_c_int] * 5 + [_c_void_p] * 10),
+    "vrwkv_ln_scatter_mean_ws_floats": (_c_long, [_c_int] * 3),
+    "vrwkv_ln_scatter_mean_fwd_bf16": (_c_int, [_c_int] * 3 + [_c_float] + [_c_void_p] * 12),
+    "vrwkv_ln_gather_mean_bwd_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 11),
     "vrwkv_adamw_step_clip_bf16": (_c_int, [ctypes.c_long] + [_c_void_p] * 5 + [ctypes.c_float] * 5 + [_c_int, _c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_long, ctypes.c_long, _c_void_p]),
     "vrwkv_sqnorm_bf16": (_c_int, [ctypes.c_long, _c_void_p, _c_void_p, _c_void_p]),
     "vrwkv_wkv7_profile_bf16": (_c_int, [_c_int] * 4 + [_c_void_p] * 18),
@@ -105,6 +108,8 @@ PROTOTYPES = {
     "vrwkv_wgrad_skinny_bf16": (_c_int, [_c_long, _c_int, _c_int] + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 2),
     "vrwkv_wgrad_big_ws_floats": (_c_long, [_c_long, _c_int, _c_int]),
     "vrwkv_wgrad_big_bf16": (_c_int, [_c_long, _c_int, _c_int] + [_c_void_p] * 5),
+    "vrwkv_patch_embed_wgrad_ws_floats": (_c_long, [_c_int] * 5),
+    "vrwkv_patch_embed_wgrad_bf16": (_c_int, [_c_int] * 5 + [_c_void_p] * 6),
     "vrwkv_stream_copy":(_c_int, [_c_void_p, _c_void_p, _c_long, _c_void_p]),
     "vrwkv_stream_probe": (_c_int, [_c_int] + [_c_void_p] * 4 + [_c_long, _c_void_p]),
     "vrwkv_transpose_bf16": (_c_int, [_c_long, _c_long, _c_void_p, _c_void_p, _c_void_p]),

@@ -467,6 +467,53 @@ class VisualTokenCompressor(nn.Module):
         return self.unpad(self.ln_out(x), num_tokens_to_pad)
 
 
+class VRWKV(nn.Module):
+    """The trainable RWKV vision encoder of VisualRWKV-v7/v7.10 (src/model.py:367-415): a Conv2d patch embedding, args.n_vrwkv_layer plain Blocks
+    (the reference hard-codes 6 VBlocks; Block 0 owns ln0), its own ln_out, and a Linear(n_embd, 1000) ImageNet head over the mean of the tokens.
+    Same sub-module names in the reference's order, so its `vrwkv.*` state-dict keys exchange strictly.  The Blocks are built from a copy of args
+    without state_tune / modality_ffn but with the language model's n_layer, which the reference's VBlock also sees and the initialisation depends
+    on.  This is the eager statement; the GPU path is fused.vrwkv_forward.
+    The reference's pad_left calls the Conv2d with token indices, so it raises whenever the token count is no multiple of 16: VRWKV exists only
+    for (image_size // patch_size)^2 % 16 == 0, which is checked here."""
+
+    def __init__(self, args):
+        super().__init__()
+        import copy
+        n_tok = (int(args.image_size) // int(args.patch_size)) ** 2
+        if n_tok % CHUNK_LEN != 0:
+            raise ValueError(f"VRWKV: (image_size // patch_size)^2 = {n_tok} tokens per image must be a multiple of {CHUNK_LEN} "
+                             "(the reference cannot pad the image tokens)")
+        self.args = args
+        bargs = copy.copy(args)
+        bargs.state_tune = 0
+        bargs.modality_ffn = 0
+        self.emb = nn.Conv2d(3, args.n_embd, kernel_size=args.patch_size, stride=args.patch_size)
+        self.blocks = nn.ModuleList([Block(bargs, i) for i in range(int(args.n_vrwkv_layer))])
+        self.ln_out = nn.LayerNorm(args.n_embd)
+        self.head = nn.Linear(args.n_embd, 1000)
+
+    def forward(self, images, scatter=None):
+        """images (B_img, 3, H, W) -> (features (B_img, L, C), logits (B_img, 1000)).  scatter = (embeds2d, row_index), fused path only: the
+        features are written into rows `row_index` of the (rows, C) token embeddings, which are returned in their place."""
+        from . import fused
+        if fused.vrwkv_supported(self, images):
+            return fused.vrwkv_forward(self, images, *(scatter or ()), grad_cp=getattr(self.args, "grad_cp", 0))
+        if scatter:
+            raise NotImplementedError("the scatter into the token embeddings is the fused path's (bf16 on the GPU, args.fused)")
+        x = self.emb(images).flatten(2).transpose(1, 2)
+        if x.size(1) % CHUNK_LEN != 0:
+            raise ValueError(f"VRWKV: {x.size(1)} tokens per image must be a multiple of {CHUNK_LEN}")
+        v_first = torch.empty_like(x)
+        for block in self.blocks:
+            if getattr(self.args, "grad_cp", 0) >= 1 and torch.is_grad_enabled():
+                from torch.utils.checkpoint import checkpoint
+                x, v_first = checkpoint(block, x, v_first, use_reentrant=False)
+            else:
+                x, v_first = block(x, v_first)
+        x = self.ln_out(x)
+        return x, self.head(x.mean(dim=1))
+
+
 class RWKV(nn.Module):
     """Embedding -> n_layer Blocks -> ln_out -> head, on already-embedded inputs (src/model.py:273-325).
 

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 from torch.nn import functional as F
 
-from .rwkv7 import IGNORE_INDEX, IMAGE_TOKEN_INDEX, L2Wrap, L2WrapWindow, RWKV, TrainCarry, VisualTokenCompressor
+from .rwkv7 import IGNORE_INDEX, IMAGE_TOKEN_INDEX, L2Wrap, L2WrapWindow, RWKV, TrainCarry, VRWKV, VisualTokenCompressor
 from .vit import SamDinoSigLIPViTBackbone
 
 
@@ -39,13 +39,14 @@ class MLPWithContextGating(nn.Module):
 
 
 def _embed(model, samples):
-    """(input embeddings, labels, keyword arguments of model.rwkv(...) for the image mask: none without args.modality_ffn).  A batch may carry
-    `n_image_tokens`, the count of IMAGE_TOKEN_INDEX in input_ids taken on the host (the collate): the routed path then needs no device
-    synchronisation to size its two GEMMs."""
+    """(input embeddings, labels, keyword arguments of model.rwkv(...) for the image mask: none without args.modality_ffn, the ImageNet logits of
+    the RWKV vision encoder or None).  A batch may carry `n_image_tokens`, the count of IMAGE_TOKEN_INDEX in input_ids taken on the host (the
+    collate): the routed path then needs no device synchronisation to size its two GEMMs."""
     res = model.preparing_embedding(samples)
     if len(res) == 2:
-        return res[0], res[1], {}
-    return res[0], res[1], {"mask": res[2], "n_image": samples.get("n_image_tokens")}
+        return res[0], res[1], {}, None
+    mk = {} if res[2] is None else {"mask": res[2], "n_image": samples.get("n_image_tokens")}
+    return res[0], res[1], mk, (res[3] if len(res) > 3 else None)
 
 
 class VisualRWKV(nn.Module):
@@ -55,6 +56,14 @@ class VisualRWKV(nn.Module):
         self.rwkv = RWKV(args)
         if len(getattr(args, "load_model", "")) > 0:
             self.from_pretrained(args.load_model)
+        if int(getattr(args, "n_vrwkv_layer", 0) or 0) > 0:
+            # v7.10 (src/model.py:419-424): encoder-free -- the trainable RWKV vision encoder takes the place of the frozen towers, the projector and
+            # the pool; with args.modality_ffn = 1 this is the reference's model
+            if int(getattr(args, "n_vtc_layer", 0) or 0) > 0:
+                raise NotImplementedError("args.n_vrwkv_layer together with args.n_vtc_layer: the compressor follows the projector of the frozen "
+                                          "towers (v7.03 / v7.04), which the RWKV vision encoder (v7.10) replaces")
+            self.vrwkv = VRWKV(args)
+            return
         self.vit = SamDinoSigLIPViTBackbone(getattr(args, "vision_tower_path", None),
                                             towers=getattr(args, "vision_towers", ("dino", "siglip", "sam")),
                                             default_image_size=getattr(args, "vision_image_size", 448),
@@ -77,6 +86,10 @@ class VisualRWKV(nn.Module):
     @property
     def has_vtc(self):
         return getattr(self, "vtc", None) is not None
+
+    @property
+    def has_vrwkv(self):
+        return getattr(self, "vrwkv", None) is not None
 
     def init_vtc_weights(self):
         """Start the compressor from the language model (src/model.py:406-412): ln_out and the first n_vtc_layer Blocks, copied.  Call it after the
@@ -101,15 +114,21 @@ class VisualRWKV(nn.Module):
 
     # ---- freezing helpers (src/model.py:368-388)
     def enable_pretrain_mode(self):
-        """v7.10's pre-training stage (src/model.py:438-443): the language model frozen except the image experts `ffn_v` / `ln_v` of every Block."""
-        if not getattr(self.args, "modality_ffn", 0):
-            raise ValueError("enable_pretrain_mode: the model has no ffn_v / ln_v (build it with args.modality_ffn = 1)")
+        """v7.10's pre-training stage (src/model.py:438-443): the RWKV vision encoder trainable, the language model frozen except the image
+        experts `ffn_v` / `ln_v` of every Block, if it has them."""
+        if not getattr(self.args, "modality_ffn", 0) and not self.has_vrwkv:
+            raise ValueError("enable_pretrain_mode: the model has no ffn_v / ln_v (build it with args.modality_ffn = 1) and no vision encoder "
+                             "(args.n_vrwkv_layer > 0)")
+        if self.has_vrwkv:
+            self.vrwkv.requires_grad_(True)
         self.rwkv.requires_grad_(False)
         for n, p in self.rwkv.named_parameters():
             if "ffn_v" in n or "ln_v" in n:
                 p.requires_grad_(True)
 
     def freeze_vit(self):
+        if self.has_vrwkv:
+            raise ValueError("freeze_vit: the model has no frozen towers (args.n_vrwkv_layer > 0); freeze `vrwkv` itself if that is meant")
         self.vit.requires_grad_(False)
 
     def freeze_rwkv(self, num_layers_to_freeze):
@@ -164,6 +183,8 @@ class VisualRWKV(nn.Module):
         plus an allocator flush and is deliberately not reproduced).  The reference encodes 4 images at a time to save
         memory; `args.vit_minibatch` raises that where the HBM allows (no activations are kept: the towers are frozen) --
         the tower GEMMs run at 0.6 PFLOP/s with 4 images (4 096 rows) and at 0.9 with 16."""
+        if getattr(self, "vrwkv", None) is not None:         # v7.10 src/model.py:501-503: (features (B_img, L, C), ImageNet logits (B_img, 1000))
+            return self.vrwkv(images["image"])
         if minibatch_size is None:
             minibatch_size = int(getattr(getattr(self, "args", None), "vit_minibatch", 4) or 4)
         keys = [k for k in ("dino", "siglip", "sam") if k in images]
@@ -199,13 +220,70 @@ class VisualRWKV(nn.Module):
 
     def preparing_embedding(self, samples):
         """(input embeddings, labels); with args.modality_ffn a third entry, the image mask (B, T, 1) bool = input_ids == IMAGE_TOKEN_INDEX
-        (v7.10 src/model.py:526)."""
+        (v7.10 src/model.py:526).  With the RWKV vision encoder (args.n_vrwkv_layer) and images in the batch, the reference's 4-tuple
+        (embeds, labels, mask, cls_logits) (src/model.py:505-526); mask is None without args.modality_ffn."""
         # called unbound, and `args` probed, because tests and the golden scripts call this method on stand-in objects that carry only
         # `rwkv`, `encode_images` and sometimes `args`
+        modality = getattr(getattr(self, "args", None), "modality_ffn", 0)
+        if getattr(self, "vrwkv", None) is not None and "images" in samples:
+            x, labels, cls_logits = VisualRWKV._preparing_embedding_vrwkv(self, samples)
+            return x, labels, ((samples["input_ids"] == IMAGE_TOKEN_INDEX).unsqueeze(-1) if modality else None), cls_logits
         res = VisualRWKV._preparing_embedding(self, samples)
-        if getattr(getattr(self, "args", None), "modality_ffn", 0):
+        if modality:
             return (*res, (samples["input_ids"] == IMAGE_TOKEN_INDEX).unsqueeze(-1))
         return res
+
+    @staticmethod
+    def _placeholder_rows(selected, n_feat):
+        """Row of the flattened token embeddings for each of n_feat feature rows, without a host synchronisation: the placeholders in order (a
+        stable sort of the mask), -1 for the surplus when there are fewer placeholders than features (the reference keeps the first features and
+        warns, src/model.py:519-523; the kernels drop a negative row both ways)."""
+        n_tok = selected.numel()
+        rows = torch.argsort(~selected, stable=True)
+        if n_feat > n_tok:                              # more features than tokens at all: the surplus has no row
+            rows = torch.cat((rows, rows.new_zeros(n_feat - n_tok)))
+            ok = torch.arange(n_feat, device=rows.device) < n_tok
+            return torch.where(ok & selected[rows], rows, torch.full_like(rows, -1)).contiguous()
+        rows = rows[:n_feat]
+        return torch.where(selected[rows], rows, torch.full_like(rows, -1)).contiguous()
+
+    def _preparing_embedding_vrwkv(self, samples):
+        """v7.10 src/model.py:505-526: every token of every image, from the RWKV vision encoder, into the placeholder rows.  Returns
+        (embeds, labels, cls_logits)."""
+        from . import fused
+        ids = samples["input_ids"]
+        B, Ln = ids.shape
+        D = self.rwkv.emb.weight.shape[1]
+        selected = ids.reshape(B * Ln) == IMAGE_TOKEN_INDEX
+        pixels = samples["images"]["image"]
+        if (getattr(self.args, "fused", False) and ids.is_cuda and self.rwkv.emb.weight.dtype == torch.bfloat16
+                and not getattr(self.args, "check_image_tokens", True) and fused.vrwkv_supported(self.vrwkv, pixels)):
+            # GPU path: ln_out of the encoder writes straight into the placeholder rows and forms the head's mean in the same pass
+            L_img = (pixels.shape[-2] // self.args.patch_size) * (pixels.shape[-1] // self.args.patch_size)
+            rows = VisualRWKV._placeholder_rows(selected, pixels.shape[0] * L_img)
+            input_embeds = self.rwkv.emb(ids.reshape(B * Ln))    # not a view: the tail op writes into it and has a second output
+            input_embeds, cls_logits = self.vrwkv(pixels, scatter=(input_embeds, rows))
+            return input_embeds.view(B, Ln, D), samples["labels"], cls_logits
+        image_features, cls_logits = self.encode_images(samples["images"])
+        image_features = image_features.reshape(-1, image_features.shape[-1])
+        input_embeds = self.rwkv.emb(ids).view(B * Ln, D)
+        n_sel = int(selected.sum()) if getattr(self.args, "check_image_tokens", True) else image_features.shape[0]
+        if n_sel != image_features.shape[0]:
+            n_feat = image_features.shape[0]
+            image_features = image_features[:n_sel]      # the reference truncates and warns (src/model.py:519-523)
+            warnings.warn(f"image tokens: {n_sel}, but image features: {n_feat}")
+        input_embeds = input_embeds.masked_scatter(selected[:, None], image_features.to(input_embeds.dtype))
+        return input_embeds.view(B, Ln, D), samples["labels"], cls_logits
+
+    def _cls_loss(self, loss, cls_logits, batch):
+        """v7.10 src/model.py:489-492: the ImageNet classification loss of the vision encoder, added when the batch carries `cls_labels`."""
+        if cls_logits is None or batch.get("cls_labels") is None:
+            return loss
+        cls_labels = batch["cls_labels"]
+        if cls_logits.shape[0] != cls_labels.shape[0]:
+            raise ValueError(f"cls_labels: {cls_labels.shape[0]} labels for {cls_logits.shape[0]} images -- the classification loss needs one image "
+                             "per sample, as in the reference")
+        return loss + F.cross_entropy(cls_logits, cls_labels)
 
     def _preparing_embedding(self, samples):
         if "images" not in samples:
@@ -292,11 +370,13 @@ class VisualRWKV(nn.Module):
         return PackedLayout(samples["seg_lens"], samples["input_ids"].shape[1], device, n_samples=samples.get("n_samples"))
 
     def forward(self, samples):
-        x, targets, mk = _embed(self, samples)
+        """(logits, targets); with the RWKV vision encoder the reference's (logits, targets, cls_logits, cls_labels) (v7.10 src/model.py:467-471)."""
+        x, targets, mk, cls_logits = _embed(self, samples)
         layout = self.packed_layout(samples, x.device)
-        if layout is not None:
-            return self.rwkv(x, layout=layout, **mk), targets
-        return self.rwkv(x, **mk), targets
+        logits = self.rwkv(x, layout=layout, **mk) if layout is not None else self.rwkv(x, **mk)
+        if getattr(self, "vrwkv", None) is not None:
+            return logits, targets, cls_logits, samples.get("cls_labels")
+        return logits, targets
 
     @staticmethod
     def loss_from_logits(logits, targets, layout=None, window=None):
@@ -338,7 +418,9 @@ class VisualRWKV(nn.Module):
         return L2Wrap.apply(loss, logits)
 
     def training_step(self, batch, batch_idx=0):
-        logits = None
+        """The language loss (loss_from_logits: L2Wrap on the language logits), plus the vision encoder's classification loss when the model has one
+        and the batch carries `cls_labels` (v7.10 src/model.py:473-493), on every branch."""
+        logits, cls = None, None
         if batch.get("seg_lens") is not None:            # a packed batch (data.pack_batches): per-segment state, shift and loss
             targets = batch["labels"]
             layout = self.packed_layout(batch, targets.device)
@@ -346,13 +428,13 @@ class VisualRWKV(nn.Module):
                 from . import fused
                 if fused.head_loss_supported(self.rwkv.head, targets):
                     plan = fused.HeadPlan(targets, 0, IGNORE_INDEX, layout)     # head + loss on the labelled rows only, per-segment weights
-                    x, _, mk = _embed(self, batch)
+                    x, _, mk, cls = _embed(self, batch)
                     h, _ = self.rwkv(x, hidden_only=True, layout=layout, **mk)
                     if fused.head_loss_supported(self.rwkv.head, targets, h):
-                        return fused.head_loss(self.rwkv.head, h, plan)
-                    return self.loss_from_logits(fused.linear(self.rwkv.head, h), targets, layout)
-            logits, targets = self(batch)
-            return self.loss_from_logits(logits, targets, layout)
+                        return self._cls_loss(fused.head_loss(self.rwkv.head, h, plan), cls, batch)
+                    return self._cls_loss(self.loss_from_logits(fused.linear(self.rwkv.head, h), targets, layout), cls, batch)
+            logits, targets, *rest = self(batch)
+            return self._cls_loss(self.loss_from_logits(logits, targets, layout), rest[0] if rest else None, batch)
         if getattr(self.args, "fused", False):
             from . import fused
             from .rwkv7 import CHUNK_LEN
@@ -361,18 +443,19 @@ class VisualRWKV(nn.Module):
                 # head + loss as one node (backward dense on the labelled rows only); the labelled rows are counted before the forward is
                 # issued, so that the head's backward finds the count in pinned memory without waiting
                 plan = fused.HeadPlan(targets, (CHUNK_LEN - targets.shape[1] % CHUNK_LEN) % CHUNK_LEN, IGNORE_INDEX)
-                x, _, mk = _embed(self, batch)
+                x, _, mk, cls = _embed(self, batch)
                 h, num_tokens_to_pad = self.rwkv(x, hidden_only=True, **mk)
                 if num_tokens_to_pad == plan.pad and fused.head_loss_supported(self.rwkv.head, targets, h):
-                    return fused.head_loss(self.rwkv.head, h, plan)
+                    return self._cls_loss(fused.head_loss(self.rwkv.head, h, plan), cls, batch)
                 logits = self.rwkv.unpad(fused.linear(self.rwkv.head, h), num_tokens_to_pad)     # RWKV.forward's head
         if logits is None:
-            logits, targets = self(batch)
+            logits, targets, *rest = self(batch)
+            cls = rest[0] if rest else None
         if getattr(self.args, "fused", False):
             from . import fused
             if fused.ce_supported(logits):
-                return fused.loss_from_logits(logits, targets, IGNORE_INDEX)
-        return self.loss_from_logits(logits, targets)
+                return self._cls_loss(fused.loss_from_logits(logits, targets, IGNORE_INDEX), cls, batch)
+        return self._cls_loss(self.loss_from_logits(logits, targets), cls, batch)
 
     def _segment_loss(self, h, targets, window):
         """The share of the row's loss that the hidden state h (B, b-a, C) of rows window = (a, b) carries (see loss_from_logits)."""
@@ -396,6 +479,10 @@ class VisualRWKV(nn.Module):
         before: no gradient crosses a cut, nothing is recomputed."""
         if batch.get("seg_lens") is not None:
             raise NotImplementedError("train_step_cut: packed rows (a batch with seg_lens) cannot be cut")
+        if getattr(self, "vrwkv", None) is not None:
+            raise NotImplementedError("train_step_cut with args.n_vrwkv_layer is not built: the classification loss shares the vision encoder's graph "
+                                      "with the embedding, which is back-propagated once at the end, and that joint backward has not been shown equal "
+                                      "to training_step's; use training_step")
         if getattr(self, "vtc", None) is not None:
             raise NotImplementedError("train_step_cut with args.n_vtc_layer is not built: the compressor's rows are not cut; use training_step")
         if getattr(self.args, "modality_ffn", 0):
@@ -468,7 +555,7 @@ class VisualRWKV(nn.Module):
         if do_sample:
             raise NotImplementedError
         samples = {"input_ids": input_ids, "images": images, "labels": torch.full_like(input_ids, IGNORE_INDEX)}
-        x, _, mk = _embed(self, samples)
+        x, _, mk, _ = _embed(self, samples)
         mk.pop("n_image", None)
         toks, lgs, prs = [], [], []
         for _ in range(max_new_tokens):
@@ -494,6 +581,9 @@ class VisualRWKV(nn.Module):
         reference's per-step re-padding changes the number of pad tokens as the sequence grows."""
         if do_sample:
             raise NotImplementedError
+        if getattr(self, "vrwkv", None) is not None:
+            raise NotImplementedError("generate_stateful with args.n_vrwkv_layer: only the embedding differs, but the stateful path has not been "
+                                      "shown equal to generate() with the vision encoder in front of it; use generate()")
         if getattr(self.args, "modality_ffn", 0):
             raise NotImplementedError("generate_stateful with args.modality_ffn: the state carries the channel-mix shift row as a LayerNorm output, and "
                                       "with two experts the next token needs that row under its own expert's LayerNorm (ln2 or ln_v), so the carried "
