@@ -236,3 +236,30 @@ def test_override_5_runs_the_plain_op_per_segment(hip_lib):
         hip_lib.vrwkv_wkv7_set_backward_variant(-1)
     _, gr = _reference_rows(ins, dy, rows)
     check_grads(list(g5), gr, "override 5, per segment")
+
+
+@pytest.mark.parametrize("variant", [8, 9])
+def test_packed_backward_batch_slices(hip_lib, variant):
+    """The launcher slices chunk_reset per row with the batch (the limit lowered here): 3 rows, another reset pattern in each, as slices of
+    2 + 1 are bit-identical to one launch."""
+    from visualrwkv_amd import wkv7
+    B, T, H = 3, 32, 2
+    rows = [[32], [16, 16], [32]]
+    *ins, dy = make_inputs(B, T, H, seed=93 + variant)
+    lay = wkv7.PackedLayout(rows, T, "cuda")
+    lay.chunk_reset.copy_(torch.tensor([[1, 0], [1, 1], [0, 1]], dtype=torch.uint8))       # resets at chunks {0}, {0, 1}, {1}
+    d, dyd = [x.cuda() for x in ins], dy.cuda()
+    per_sample = T * H * 64 * 4
+    assert hip_lib.vrwkv_wkv7_set_backward_variant(variant) == 0
+    try:
+        _, s, sa, base = _run_packed(d, dyd, lay)
+        assert hip_lib.vrwkv_wkv7_last_variant(1) == variant
+        assert hip_lib.vrwkv_wkv7_set_backward_slice_limit(2 * per_sample + 1) == 0
+        sliced = wkv7.wkv7_backward_packed(*d, dyd, s, sa, lay)
+        torch.cuda.synchronize()
+        assert hip_lib.vrwkv_wkv7_last_variant(1) == variant
+        for n, o, r in zip(NAMES, sliced, base):
+            assert torch.equal(o, r), n
+    finally:
+        hip_lib.vrwkv_wkv7_set_backward_slice_limit(0)
+        hip_lib.vrwkv_wkv7_set_backward_variant(-1)

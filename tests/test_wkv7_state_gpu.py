@@ -109,6 +109,38 @@ def test_split_identity_at_the_bench_shape(hip_lib):
         bf16_close(torch.cat([a_, b_], dim=1), r.float(), f"chained {n}", tol=TOL, max_flip=FLIP_W if n in ("dw", "dz") else FLIP_G)
 
 
+@pytest.mark.parametrize("variant", [-1, 9])                # -1: schedule 8 at this size
+def test_state_backward_batch_slices(hip_lib, variant):
+    """The launcher slices s0 / ds_final / ds0 per sample with the batch (tensors of 4 GiB and more in production; the limit lowered here):
+    3 samples as slices of 2 + 1 are bit-identical to one launch, a single sample above the limit goes to the 64-bit kernel (variant 5)."""
+    from visualrwkv_amd import wkv7
+    B, T, H = 3, 32, 2
+    ins, dy, s0, dsT = state_inputs(B, T, H, seed=92 + variant)
+    _, _, gr, ds0r = reference(ins, dy, s0, dsT)
+    d, s0d = [x.cuda() for x in ins], s0.cuda()
+    _, _, s, sa = _fwd(d, s0d)
+    args = (*d, dy.cuda(), s, sa, s0d, dsT.cuda(), True)
+    per_sample = T * H * 64 * 4
+    assert hip_lib.vrwkv_wkv7_set_backward_variant(variant) == 0
+    try:
+        base = wkv7.wkv7_backward_state(*args)
+        assert hip_lib.vrwkv_wkv7_set_backward_slice_limit(2 * per_sample + 1) == 0
+        sliced = wkv7.wkv7_backward_state(*args)
+        torch.cuda.synchronize()
+        assert hip_lib.vrwkv_wkv7_last_variant(1) == (8 if variant == -1 else variant)
+        for n, o, r in zip(NAMES + ("ds0",), sliced, base):
+            assert torch.equal(o, r), n
+        assert hip_lib.vrwkv_wkv7_set_backward_slice_limit(per_sample // 2) == 0
+        *wide, wide_ds0 = wkv7.wkv7_backward_state(*args)
+        torch.cuda.synchronize()
+        assert hip_lib.vrwkv_wkv7_last_variant(1) == 5
+    finally:
+        hip_lib.vrwkv_wkv7_set_backward_slice_limit(0)
+        hip_lib.vrwkv_wkv7_set_backward_variant(-1)
+    check_grads(wide, gr, f"one sample above the limit, override {variant}")
+    assert rel_rms64(wide_ds0.cpu(), ds0r) < DS_TOL
+
+
 def _visual(grad_cp):
     from visualrwkv_amd.visual import VisualRWKV
     args = SimpleNamespace(n_embd=2048, n_layer=2, dim_att=2048, head_size_a=64, head_size_divisor=8, vocab_size=65536,

@@ -28,14 +28,14 @@ extern "C" int vrwkv_wkv7_profile_bf16(int backward, int B, int T, int H, const 
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((long)B * H));
     if (!backward) {
-        const wkv7::FwdArgs p{T, H, (const uint16_t*)w, (const uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v,
-                              (const uint16_t*)z, (const uint16_t*)a, (uint16_t*)y, s, sa, dbg};
+        wkv7::FwdArgs p = fwd_args(T, H, w, q, k, v, z, a, y, s, sa);
+        p.dbg = dbg;
         if (g_fwd_variant == 7 || g_fwd_variant == -1) return launch_lds(&wkv7f4::fwd_kernel_v4<true>, grid, dim3(512), sizeof(wkv7f4::LdsF4), st, p);
         return launch_lds(&wkv7c::fwd_kernel_v3<true, false, 1, 1, false, true, true>, grid, dim3(512), sizeof(wkv7c::LdsF), st, p);
     }
-    const wkv7::BwdArgs p{T, H, (const uint16_t*)w, (const uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v,
-                          (const uint16_t*)z, (const uint16_t*)a, (const uint16_t*)dy, s, sa,
-                          (uint16_t*)dw, (uint16_t*)dq, (uint16_t*)dk, (uint16_t*)dv, (uint16_t*)dz, (uint16_t*)da, dbg};
+    BwdCall c{w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da};
+    c.dbg = dbg;
+    const wkv7::BwdArgs p = bwd_args(c, T, H);
 #ifdef VRWKV_V6_EXPERIMENTS
     if (backward == 3 || (backward >= 20 && backward < 28)) return wkv7exp::launch_profile(backward, grid, st, p);
 #endif

@@ -192,6 +192,9 @@ def load_host() -> ctypes.CDLL:
     return lib
 
 
+ESHAPE = -2       # VRWKV_ESHAPE (include/visualrwkv_hip.h): an entry has no kernel for this shape; some callers handle it themselves
+
+
 def check(code: int, what: str) -> None:
     if code != 0:
         msg = load().vrwkv_strerror(code).decode()

@@ -56,13 +56,45 @@ def _timed(kind, elems, stream_dev, fn):
     return rc
 
 
-def _check_act(name, t, B, T, H):
-    if t.dtype != torch.bfloat16:
-        raise TypeError(f"wind_backstepping: {name} must be bfloat16, got {t.dtype}")
-    if tuple(t.shape) != (B, T, H, HEAD_SIZE):
-        raise ValueError(f"wind_backstepping: {name} has shape {tuple(t.shape)}, expected {(B, T, H, HEAD_SIZE)}")
-    if not t.is_contiguous():
-        raise ValueError(f"wind_backstepping: {name} must be contiguous")
+def _call(name, kind, w, *args, allow=()):
+    """One launch of the library entry `name` on w's device and PyTorch's current stream there.  The entry gets w's leading sizes ((B, T, H);
+    (B, H) for the step), then `args` -- tensors as pointers, None as NULL, numbers as they are -- then the stream.  kind: the EVENT_LOG key
+    (None: the launch is not logged).  Returns the entry's code, which is 0 or one of `allow`: anything else raises (hip_lib.check)."""
+    fn = getattr(hip_lib.load(), name)
+    ptrs = [0 if x is None else x.data_ptr() if isinstance(x, torch.Tensor) else x for x in args]
+    with torch.cuda.device(w.device):
+        stream = torch.cuda.current_stream(w.device).cuda_stream
+        launch = lambda: fn(*w.shape[:-1], *ptrs, stream)
+        rc = launch() if kind is None else _timed(kind, w.numel(), w.device, launch)
+    if rc not in allow:
+        hip_lib.check(rc, name)
+    return rc
+
+
+def _byproducts(w):
+    """Buffers for what the training forward leaves for the backward: the chunk checkpoints `s` and `sa`."""
+    B, T, H, C = w.shape
+    return (torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device),
+            torch.empty(B, T, H, C, dtype=torch.float32, device=w.device))
+
+
+def _check_acts(names, tensors, B, T, H, device):
+    for name, t in zip(names, tensors):
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"wind_backstepping: {name} must be bfloat16, got {t.dtype}")
+        if tuple(t.shape) != (B, T, H, HEAD_SIZE):
+            raise ValueError(f"wind_backstepping: {name} has shape {tuple(t.shape)}, expected {(B, T, H, HEAD_SIZE)}")
+        if not t.is_contiguous():
+            raise ValueError(f"wind_backstepping: {name} must be contiguous")
+        if t.device != device:
+            raise ValueError("wind_backstepping: all tensors must live on the same device")
+
+
+def _check_state0(name, t, B, H, device):
+    """A carried state or its gradient: None, or contiguous fp32 (B,H,64,64) on `device`."""
+    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, H, HEAD_SIZE, HEAD_SIZE)
+                          or t.device != device):
+        raise ValueError(f"wkv7: {name} must be a contiguous fp32 ({B},{H},{HEAD_SIZE},{HEAD_SIZE}) tensor on {device}")
 
 
 def _check_state(s, sa, B, T, H, dev):
@@ -85,38 +117,22 @@ def _dims(w):
     return B, T, H
 
 
+_IN_NAMES = ("w", "q", "k", "v", "z", "a")
+_GRAD_NAMES = ("dw", "dq", "dk", "dv", "dz", "da")
+
+
 def _forward_hip(w, q, k, v, z, a, y, s, sa):
     B, T, H = _dims(w)
-    for n, t in zip("wqkvzay", (w, q, k, v, z, a, y)):
-        _check_act(n, t, B, T, H)
-        if t.device != w.device:
-            raise ValueError("wind_backstepping: all tensors must live on the same device")
+    _check_acts(_IN_NAMES + ("y",), (w, q, k, v, z, a, y), B, T, H, w.device)
     _check_state(s, sa, B, T, H, w.device)
-    lib = hip_lib.load()
-    with torch.cuda.device(w.device):
-        stream = torch.cuda.current_stream(w.device).cuda_stream
-        rc = _timed("fwd", B * T * H * HEAD_SIZE, w.device, lambda: lib.vrwkv_wkv7_forward_bf16(
-            B, T, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(), a.data_ptr(),
-            y.data_ptr(), s.data_ptr(), sa.data_ptr(), stream))
-    hip_lib.check(rc, "vrwkv_wkv7_forward_bf16")
+    _call("vrwkv_wkv7_forward_bf16", "fwd", w, w, q, k, v, z, a, y, s, sa)
 
 
 def _backward_hip(w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da):
     B, T, H = _dims(w)
-    names = ("w", "q", "k", "v", "z", "a", "dy", "dw", "dq", "dk", "dv", "dz", "da")
-    for n, t in zip(names, (w, q, k, v, z, a, dy, dw, dq, dk, dv, dz, da)):
-        _check_act(n, t, B, T, H)
-        if t.device != w.device:
-            raise ValueError("wind_backstepping: all tensors must live on the same device")
+    _check_acts(_IN_NAMES + ("dy",) + _GRAD_NAMES, (w, q, k, v, z, a, dy, dw, dq, dk, dv, dz, da), B, T, H, w.device)
     _check_state(s, sa, B, T, H, w.device)
-    lib = hip_lib.load()
-    with torch.cuda.device(w.device):
-        stream = torch.cuda.current_stream(w.device).cuda_stream
-        rc = _timed("bwd", B * T * H * HEAD_SIZE, w.device, lambda: lib.vrwkv_wkv7_backward_bf16(
-            B, T, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(), a.data_ptr(),
-            dy.data_ptr(), s.data_ptr(), sa.data_ptr(), dw.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-            dv.data_ptr(), dz.data_ptr(), da.data_ptr(), stream))
-    hip_lib.check(rc, "vrwkv_wkv7_backward_bf16")
+    _call("vrwkv_wkv7_backward_bf16", "bwd", w, w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da)
 
 
 HOST_THREADS = int(os.environ.get("VRWKV_HOST_THREADS", "0"))     # 0 = every hardware thread
@@ -152,8 +168,7 @@ def _forward_host(w, q, k, v, z, a, y, s, sa):
 
 
 def _backward_host(w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da):
-    names = ("w", "q", "k", "v", "z", "a", "dy", "dw", "dq", "dk", "dv", "dz", "da")
-    B, T, H, code = _host_dtype(w, (w, q, k, v, z, a, dy, dw, dq, dk, dv, dz, da), names)
+    B, T, H, code = _host_dtype(w, (w, q, k, v, z, a, dy, dw, dq, dk, dv, dz, da), _IN_NAMES + ("dy",) + _GRAD_NAMES)
     _check_state(s, sa, B, T, H, w.device)
     rc = hip_lib.load_host().vrwkv_wkv7_backward_host(B, T, H, code, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(),
                                                  a.data_ptr(), dy.data_ptr(), s.data_ptr(), sa.data_ptr(), dw.data_ptr(), dq.data_ptr(),
@@ -161,7 +176,7 @@ def _backward_host(w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da):
     _check_host(rc, "vrwkv_wkv7_backward_host")
 
 
-def _no_cpu(*args):
+def _no_cpu():
     raise NotImplementedError("this WKV7 entry point (stateful step / prefill) has no CPU implementation; move the tensors to an "
                               "MI355X device.  The training op torch.ops.wind_backstepping does run on CPU tensors.")
 
@@ -228,8 +243,7 @@ class WindBackstepping(torch.autograd.Function):
             y, _, s, sa = wkv7_forward_tparallel(w, q, k, v, z, b, segments=P, train=True)
         else:
             y = torch.empty_like(v)
-            s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
-            sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+            s, sa = _byproducts(w)
             torch.ops.wind_backstepping.forward(w, q, k, v, z, b, y, s, sa)
         ctx.save_for_backward(w, q, k, v, z, b, s, sa)
         return y
@@ -238,9 +252,7 @@ class WindBackstepping(torch.autograd.Function):
     def backward(ctx, dy):
         if ctx.recompute:
             w, q, k, v, z, b = ctx.saved_tensors
-            B, T, H, C = w.shape
-            s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
-            sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+            s, sa = _byproducts(w)
             torch.ops.wind_backstepping.forward(w, q, k, v, z, b, torch.empty_like(v), s, sa)
         else:
             w, q, k, v, z, b, s, sa = ctx.saved_tensors
@@ -293,23 +305,13 @@ def wkv7_backward_state(w, q, k, v, z, a, dy, s, sa, state0=None, ds_final=None,
     """vrwkv_wkv7_backward_state_bf16: the training backward from a forward that started at `state0` (None = zeros) with dL/d(state_T) =
     `ds_final` (None = zeros).  Returns (dw, dq, dk, dv, dz, da, ds0 or None); states are (B,H,64,64) fp32, [value row][key column]."""
     B, T, H = _dims(w)
-    for n, t in zip(("w", "q", "k", "v", "z", "a", "dy"), (w, q, k, v, z, a, dy)):
-        _check_act(n, t, B, T, H)
+    _check_acts(_IN_NAMES + ("dy",), (w, q, k, v, z, a, dy), B, T, H, w.device)
     _check_state(s, sa, B, T, H, w.device)
-    for n, t in (("state0", state0), ("ds_final", ds_final)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, H, HEAD_SIZE, HEAD_SIZE)
-                              or t.device != w.device):
-            raise ValueError(f"wkv7: {n} must be a contiguous fp32 ({B},{H},{HEAD_SIZE},{HEAD_SIZE}) tensor on {w.device}")
+    _check_state0("state0", state0, B, H, w.device)
+    _check_state0("ds_final", ds_final, B, H, w.device)
     grads = [torch.empty_like(w) for _ in range(6)]
     ds0 = torch.empty(B, H, HEAD_SIZE, HEAD_SIZE, dtype=torch.float32, device=w.device) if want_ds0 else None
-    lib = hip_lib.load()
-    ptr = lambda t: t.data_ptr() if t is not None else 0
-    with torch.cuda.device(w.device):
-        stream = torch.cuda.current_stream(w.device).cuda_stream
-        rc = _timed("bwd_state", B * T * H * HEAD_SIZE, w.device, lambda: lib.vrwkv_wkv7_backward_state_bf16(
-            B, T, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(), a.data_ptr(), dy.data_ptr(),
-            s.data_ptr(), sa.data_ptr(), ptr(state0), ptr(ds_final), ptr(ds0), *[g.data_ptr() for g in grads], stream))
-    hip_lib.check(rc, "vrwkv_wkv7_backward_state_bf16")
+    _call("vrwkv_wkv7_backward_state_bf16", "bwd_state", w, w, q, k, v, z, a, dy, s, sa, state0, ds_final, ds0, *grads)
     return (*grads, ds0)
 
 
@@ -347,8 +349,7 @@ class WindBacksteppingState(torch.autograd.Function):
             y, fin = wkv7_forward_state(w, q, k, v, z, b, state0, want_state=True)
             ctx.save_for_backward(w, q, k, v, z, b, state0)
             return y, fin
-        s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
-        sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+        s, sa = _byproducts(w)
         y, fin = wkv7_forward_state(w, q, k, v, z, b, state0, want_state=True, s_ckpt=s, sa=sa)
         ctx.save_for_backward(w, q, k, v, z, b, state0, s, sa)
         return y, fin
@@ -371,9 +372,7 @@ class WindBacksteppingState(torch.autograd.Function):
             return (*g[:6], g[6] if want_ds0 else None, None)
         if ctx.recompute:
             w, q, k, v, z, b, state0 = ctx.saved_tensors
-            B, T, H, C = w.shape
-            s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
-            sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+            s, sa = _byproducts(w)
             wkv7_forward_state(w, q, k, v, z, b, state0, want_state=False, s_ckpt=s, sa=sa)
         else:
             w, q, k, v, z, b, state0, s, sa = ctx.saved_tensors
@@ -457,25 +456,15 @@ class PackedLayout:
 def wkv7_forward_packed(w, q, k, v, z, a, layout, s_ckpt=None, sa=None):
     """vrwkv_wkv7_forward_packed_bf16: y of a packed batch; with buffers s_ckpt (B,H,T/16,64,64) / sa (B,T,H,64) also the training by-products."""
     B, T, H = _dims(w)
-    for n, t in zip("wqkvza", (w, q, k, v, z, a)):
-        _check_act(n, t, B, T, H)
+    _check_acts(_IN_NAMES, (w, q, k, v, z, a), B, T, H, w.device)
     layout.check(B, T, w.device)
     if (s_ckpt is None) != (sa is None):
         raise ValueError("wkv7: s_ckpt and sa go together")
     if s_ckpt is not None:
         _check_state(s_ckpt, sa, B, T, H, w.device)
     y = torch.empty_like(v)
-    lib = hip_lib.load()
-    with torch.cuda.device(w.device):
-        stream = torch.cuda.current_stream(w.device).cuda_stream
-        rc = _timed("fwd_packed", B * T * H * HEAD_SIZE, w.device, lambda: lib.vrwkv_wkv7_forward_packed_bf16(
-            B, T, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(), a.data_ptr(), y.data_ptr(),
-            layout.chunk_reset.data_ptr(), s_ckpt.data_ptr() if s_ckpt is not None else 0, sa.data_ptr() if sa is not None else 0, stream))
-    hip_lib.check(rc, "vrwkv_wkv7_forward_packed_bf16")
+    _call("vrwkv_wkv7_forward_packed_bf16", "fwd_packed", w, w, q, k, v, z, a, y, layout.chunk_reset, s_ckpt, sa)
     return y
-
-
-_ESHAPE = -2          # VRWKV_ESHAPE
 
 
 def wkv7_backward_packed(w, q, k, v, z, a, dy, s, sa, layout):
@@ -483,18 +472,13 @@ def wkv7_backward_packed(w, q, k, v, z, a, dy, s, sa, layout):
     override at 5, a single row of 4 GiB and more) the plain op runs once per segment on contiguous slices; `s` and `sa` of the packed forward
     are, segment by segment, what it wants."""
     B, T, H = _dims(w)
-    for n, t in zip(("w", "q", "k", "v", "z", "a", "dy"), (w, q, k, v, z, a, dy)):
-        _check_act(n, t, B, T, H)
+    _check_acts(_IN_NAMES + ("dy",), (w, q, k, v, z, a, dy), B, T, H, w.device)
     _check_state(s, sa, B, T, H, w.device)
     layout.check(B, T, w.device)
     grads = [torch.empty_like(w) for _ in range(6)]
-    lib = hip_lib.load()
-    with torch.cuda.device(w.device):
-        stream = torch.cuda.current_stream(w.device).cuda_stream
-        rc = _timed("bwd_packed", B * T * H * HEAD_SIZE, w.device, lambda: lib.vrwkv_wkv7_backward_packed_bf16(
-            B, T, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(), a.data_ptr(), dy.data_ptr(),
-            s.data_ptr(), sa.data_ptr(), layout.chunk_reset.data_ptr(), *[g.data_ptr() for g in grads], stream))
-    if rc == _ESHAPE:
+    rc = _call("vrwkv_wkv7_backward_packed_bf16", "bwd_packed", w, w, q, k, v, z, a, dy, s, sa, layout.chunk_reset, *grads,
+               allow=(hip_lib.ESHAPE,))
+    if rc == hip_lib.ESHAPE:
         for b, t0, t1 in layout.segments:
             cut = [x[b:b + 1, t0:t1].contiguous() for x in (w, q, k, v, z, a, dy)]
             part = [torch.empty_like(cut[0]) for _ in range(6)]
@@ -502,8 +486,6 @@ def wkv7_backward_packed(w, q, k, v, z, a, dy, s, sa, layout):
             for g, x in zip(grads, part):
                 g[b:b + 1, t0:t1] = x
             grads[0][b, t0] = 0                     # as the packed kernel: dL/dw of a sample's first token is exactly 0
-        return tuple(grads)
-    hip_lib.check(rc, "vrwkv_wkv7_backward_packed_bf16")
     return tuple(grads)
 
 
@@ -527,8 +509,7 @@ class WindBacksteppingPacked(torch.autograd.Function):
         if ctx.recompute:                                # y only; the backward regenerates s and sa
             ctx.save_for_backward(w, q, k, v, z, b)
             return wkv7_forward_packed(w, q, k, v, z, b, layout)
-        s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
-        sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+        s, sa = _byproducts(w)
         y = wkv7_forward_packed(w, q, k, v, z, b, layout, s_ckpt=s, sa=sa)
         ctx.save_for_backward(w, q, k, v, z, b, s, sa)
         return y
@@ -537,9 +518,7 @@ class WindBacksteppingPacked(torch.autograd.Function):
     def backward(ctx, dy):
         if ctx.recompute:
             w, q, k, v, z, b = ctx.saved_tensors
-            B, T, H, C = w.shape
-            s = torch.empty(B, H, T // CHUNK_LEN, C, C, dtype=torch.float32, device=w.device)
-            sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device)
+            s, sa = _byproducts(w)
             wkv7_forward_packed(w, q, k, v, z, b, ctx.layout, s_ckpt=s, sa=sa)
         else:
             w, q, k, v, z, b, s, sa = ctx.saved_tensors
@@ -580,26 +559,15 @@ def wkv7_forward_state(w, q, k, v, z, a, state0=None, want_state=True, s_ckpt=No
     The kernel neither writes the chunk checkpoints nor `sa` (22 of the training forward's 24 output bytes per element)
     unless the caller passes buffers for them (s_ckpt (B,H,T/16,64,64), sa (B,T,H,64), fp32)."""
     B, T, H = _dims(w)
-    for n, t in zip("wqkvza", (w, q, k, v, z, a)):
-        _check_act(n, t, B, T, H)
-    if state0 is not None and (state0.dtype != torch.float32 or not state0.is_contiguous()
-                               or tuple(state0.shape) != (B, H, HEAD_SIZE, HEAD_SIZE) or state0.device != w.device):
-        raise ValueError(f"wkv7: state0 must be a contiguous fp32 ({B},{H},{HEAD_SIZE},{HEAD_SIZE}) tensor on {w.device}")
+    _check_acts(_IN_NAMES, (w, q, k, v, z, a), B, T, H, w.device)
+    _check_state0("state0", state0, B, H, w.device)
     if (s_ckpt is None) != (sa is None):
         raise ValueError("wkv7: s_ckpt and sa go together")
     if s_ckpt is not None:
         _check_state(s_ckpt, sa, B, T, H, w.device)
     y = torch.empty_like(v)
     s_fin = torch.empty(B, H, HEAD_SIZE, HEAD_SIZE, dtype=torch.float32, device=w.device) if want_state else None
-    lib = hip_lib.load()
-    with torch.cuda.device(w.device):
-        stream = torch.cuda.current_stream(w.device).cuda_stream
-        rc = _timed("fwd_state", B * T * H * HEAD_SIZE, w.device, lambda: lib.vrwkv_wkv7_forward_state_bf16(
-            B, T, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(),
-            a.data_ptr(), y.data_ptr(), state0.data_ptr() if state0 is not None else 0,
-            s_fin.data_ptr() if want_state else 0,
-            s_ckpt.data_ptr() if s_ckpt is not None else 0, sa.data_ptr() if sa is not None else 0, stream))
-    hip_lib.check(rc, "vrwkv_wkv7_forward_state_bf16")
+    _call("vrwkv_wkv7_forward_state_bf16", "fwd_state", w, w, q, k, v, z, a, y, state0, s_fin, s_ckpt, sa)
     return y, s_fin
 
 
@@ -636,8 +604,7 @@ def wkv7_forward_tparallel(w, q, k, v, z, a, state0=None, segments=None, train=F
     if P <= 1:
         if not train:
             return wkv7_forward_state(w, q, k, v, z, a, state0)
-        s = torch.empty(B, H, T // CHUNK_LEN, HEAD_SIZE, HEAD_SIZE, dtype=torch.float32, device=w.device)
-        sa = torch.empty(B, T, H, HEAD_SIZE, dtype=torch.float32, device=w.device)
+        s, sa = _byproducts(w)
         y, fin = wkv7_forward_state(w, q, k, v, z, a, state0, s_ckpt=s, sa=sa)
         return y, fin, s, sa
     if T % P != 0 or (T // P) % CHUNK_LEN != 0:
@@ -681,20 +648,12 @@ def wkv7_backward_tparallel(w, q, k, v, z, a, dy, s, sa, segments):
     P = int(segments)
     if P < 1 or T % P != 0 or (T // P) % CHUNK_LEN != 0:
         raise ValueError(f"wkv7: T = {T} cannot be cut into {P} segments of whole {CHUNK_LEN}-token chunks")
-    for n, t in zip(("w", "q", "k", "v", "z", "a", "dy"), (w, q, k, v, z, a, dy)):
-        _check_act(n, t, B, T, H)
+    _check_acts(_IN_NAMES + ("dy",), (w, q, k, v, z, a, dy), B, T, H, w.device)
     _check_state(s, sa, B, T, H, w.device)
     grads = [torch.empty_like(w) for _ in range(6)]
-    lib = hip_lib.load()
 
     def launch(ds_in, ds_out):
-        with torch.cuda.device(w.device):
-            rc = lib.vrwkv_wkv7_backward_segments_bf16(
-                B, T, H, P, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(), a.data_ptr(), dy.data_ptr(),
-                s.data_ptr(), sa.data_ptr(), ds_in.data_ptr() if ds_in is not None else 0,
-                ds_out.data_ptr() if ds_out is not None else 0, *[g.data_ptr() for g in grads],
-                torch.cuda.current_stream(w.device).cuda_stream)
-        hip_lib.check(rc, "vrwkv_wkv7_backward_segments_bf16")
+        _call("vrwkv_wkv7_backward_segments_bf16", None, w, P, w, q, k, v, z, a, dy, s, sa, ds_in, ds_out, *grads)
 
     if P == 1:
         launch(None, None)
@@ -727,10 +686,5 @@ def wkv7_step(w, q, k, v, z, a, state):
             or state.device != w.device):
         raise ValueError(f"wkv7_step: state must be a contiguous fp32 ({B},{H},{C},{C}) tensor on {w.device}")
     y = torch.empty_like(v)
-    lib = hip_lib.load()
-    with torch.cuda.device(w.device):
-        rc = lib.vrwkv_wkv7_step_bf16(B, H, w.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), z.data_ptr(),
-                                      a.data_ptr(), state.data_ptr(), y.data_ptr(),
-                                      torch.cuda.current_stream(w.device).cuda_stream)
-    hip_lib.check(rc, "vrwkv_wkv7_step_bf16")
+    _call("vrwkv_wkv7_step_bf16", None, w, w, q, k, v, z, a, state, y)
     return y
