@@ -1,6 +1,8 @@
 """BASELINE config 4 as a parity/sanity run (not the bench.py line): VisualRWKV-6 7B (L32, C4096, WKV6 kernels) +
 CLIP ViT-L/14-336 (random init from the transformers config), 576+1 image tokens + 2048 text tokens, bf16, full train
-step with the ZeRO-1 engine on one MI355X.   python benchmarks/bench_v6.py [--micro-bsz 2] [--layers 32]"""
+step with the ZeRO-1 engine on one MI355X.   python benchmarks/bench_v6.py [--micro-bsz 2] [--layers 32]
+--image-state 1: the v6.xx model instead (visual6.py, args.image_state): the 577 image rows are a per-layer WKV state prefix, not context
+tokens; every Block runs twice (image rows from zeros, text rows from the state that pass ends in)."""
 import argparse
 import json
 import os
@@ -23,6 +25,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--grad-cp", type=int, default=0)
     ap.add_argument("--fused", type=int, default=1, help="fused RWKV-6 glue kernels (ddmix, gn_silu, add+LN, loss)")
+    ap.add_argument("--image-state", type=int, default=0, help="1: v6.xx, the image as a per-layer WKV state (RUN_CUDA_RWKV6_STATE)")
     a = ap.parse_args()
     import transformers
     from visualrwkv_amd import build, wkv6
@@ -36,7 +39,7 @@ def main():
     C = a.n_embd
     args = SimpleNamespace(n_embd=C, dim_att=C, n_layer=a.layers, head_size_a=64, head_size_divisor=8,
                            dim_ffn=int((C * 3.5) // 32 * 32), vocab_size=65536, dropout=0, grad_cp=a.grad_cp, ctx_len=4096,
-                           load_model="", grid_size=-1, fused=bool(a.fused))
+                           load_model="", grid_size=-1, fused=bool(a.fused), image_state=a.image_state)
     clip_cfg = transformers.CLIPVisionConfig(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24,
                                              num_attention_heads=16, image_size=336, patch_size=14)
     torch.manual_seed(42)
@@ -81,7 +84,9 @@ def main():
     log, wkv6.EVENT_LOG = wkv6.EVENT_LOG, None
     losses = [float(x) if torch.is_tensor(x) else x for x in losses]
     dt = (time.perf_counter() - t0) / a.steps
-    T = T_text + 577
+    T = T_text + 577                                  # rows through every Block per sample; with --image-state 1 the text right of the image token (T_text - 4) + 577
+    if a.image_state:
+        T = T_text - 4 + 577
     n_par = sum(p.numel() for p in model.rwkv.parameters())
     # in-step WKV6 kernels against the 8 TB/s roofline, bytes as benchmarks/wkv6_micro.py counts them (r,k,v bf16 + ew f32 + y, plus the
     # 16 B / element chunk-state checkpoint this implementation writes in the forward and reads in the backward)
@@ -90,13 +95,13 @@ def main():
     for kind, bpe in (("fwd", FWD_B), ("bwd", BWD_B)):
         ms = [e0.elapsed_time(e1) for k_, e0, e1, _ in log if k_ == kind]
         if ms:
-            elems = next(n for k_, _, _, n in log if k_ == kind)
+            elems = sum(n for k_, _, _, n in log if k_ == kind) / len(ms)          # --image-state: launches of two sizes; the average pairs with avg_ms
             avg = sum(ms) / len(ms)
             wkv[kind] = {"avg_ms": round(avg, 4), "launches": len(ms), "bytes_per_elem": bpe, "achieved_GBps": round(elems * bpe / (avg * 1e-3) / 1e9, 1),
                          "frac_of_8TBps": round(elems * bpe / (avg * 1e-3) / 8e12, 4)}
     print(json.dumps({"config": "cfg4: VisualRWKV-6 %dL C%d + CLIP ViT-L/14-336" % (a.layers, C), "wkv6_in_step": wkv, "lm_params_B": round(n_par / 1e9, 2),
                       "micro_bsz": B, "seq_len": T, "tokens_per_s": round(B * T / dt), "ms_per_step": round(dt * 1e3, 1),
-                      "losses": [round(x, 3) for x in losses], "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2**30, 1), "grad_cp": a.grad_cp, "fused": bool(a.fused)}))
+                      "losses": [round(x, 3) for x in losses], "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2**30, 1), "grad_cp": a.grad_cp, "fused": bool(a.fused), "image_state": a.image_state}))
 
 
 if __name__ == "__main__":

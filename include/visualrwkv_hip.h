@@ -123,6 +123,23 @@ int vrwkv_wkv6_forward_bf16(int B, int T, int C, int H, const void* r, const voi
 int vrwkv_wkv6_backward_bf16(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* ew,
                              const void* u, const void* gy, const float* s_ckpt, void* gr, void* gk, void* gv, void* gw,
                              void* gu, void* stream);
+/* WKV6 with a carried state: what VisualRWKV-v6/v6.xx/src/model.py:35-42 (RUN_CUDA_RWKV6_STATE, over fla's
+ * fused_recurrent_rwkv6(initial_state=, output_final_state=True)) computes, with its backward.  Everything as above, plus four
+ * states, each (B,H,64,64) f32 laid out [key j][value i] (fla's (B,H,K,V); the layout of one chunk checkpoint), each optional:
+ *   state0    in : the state before token 0                 NULL = zeros
+ *   state_T   out: the state after token T-1 (any T >= 1)   NULL = not wanted
+ *   d_state_T in : dL/d(state_T)                            NULL = zeros
+ *   d_state0  out: dL/d(state0)                             NULL = not wanted
+ * The forward's checkpoint of chunk 0 holds state0, so the backward takes no state0: give it the s_ckpt of the forward that
+ * got the state.  Same checks and return codes as the plain entries (every non-NULL pointer 16-byte aligned); with all four
+ * NULL they run the plain entries' kernels and give their results bit for bit.  Launches of 4 GiB and more are cut into batch
+ * slices as in the plain backward (the state pointers advance with the samples); both backward kernel generations take the
+ * state. */
+int vrwkv_wkv6_forward_state_bf16(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* ew,
+                                  const void* u, const float* state0, void* y, float* state_T, float* s_ckpt, void* stream);
+int vrwkv_wkv6_backward_state_bf16(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* ew,
+                                   const void* u, const void* gy, const float* s_ckpt, const float* d_state_T, void* gr, void* gk,
+                                   void* gv, void* gw, void* gu, float* d_state0, void* stream);
 /* Kernel generation of the WKV6 backward (same-box A/B in benchmarks): -1 = default (2), 2 = three-role pipeline of 12 waves
  * (csrc/wkv6_bwd_v2.h), 1 = the four-wave kernel of rounds 1-3 (csrc/wkv6_chunked.h).  Anything else: VRWKV_EINVAL. */
 int vrwkv_wkv6_set_backward_variant(int variant);

@@ -155,6 +155,16 @@ DEVFN void s0_lean6(float* img, const float* s_chunk, const Lean6& ll) {
     lds_dma16_lean<2048>(base, ll.vs[2], d); lds_dma16_lean<3072>(base, ll.vs[3], d);
 }
 
+// STATE (vrwkv_wkv6_backward_state_bf16): the training op with a carried state.  Only the prologue and the epilogue change:
+//   * d_state_T[b,h] (null = zeros) is one more 16 KB [j][i] fp32 matrix in the checkpoints' layout: the P waves request it with their first
+//     requests (dma_state, the S0 path) into the S0 ring slot (nchunk % 3) that no checkpoint uses before step 1, and the I and J waves take
+//     their copies of dL/dS from it, each in its own tile orientation, between the first barrier and the barrier of step 0 -- the slot's
+//     first checkpoint request (chunk nchunk - 3, step 1) comes after that barrier;
+//   * d_state0[b,h] (null = not wanted) is dL/dS after chunk 0's update, written by the J waves from their [i][j] copy dS2 after the last
+//     step: 4 x 16-byte stores per lane.  The I waves' copy dS1 holds the same sums in another MFMA order and is not written.
+//   S0 of chunk 0 is the forward's checkpoint 0 = state0, requested like every other; the decay-gradient term of chunk 0 reads it as any chunk's.
+// No new barrier, no new LDS image, no change to a steady-state step.  With STATE off every `if (STATE ...)` folds away.
+template <bool STATE = false>
 __global__ __launch_bounds__(768) void bwd6_kernel_v2(Bwd6Args p) {
     Lds6V2& lds = *reinterpret_cast<Lds6V2*>(dyn_lds());
     const int T = p.T, H = p.H;
@@ -194,6 +204,7 @@ __global__ __launch_bounds__(768) void bwd6_kernel_v2(Bwd6Args p) {
             dma_rows6(lds, p, head_base + (size_t)cl * L * ts, cl, w, ts, lane, valid);
             if (cl >= 1) dma_rows6(lds, p, head_base + (size_t)(cl - 1) * L * ts, cl - 1, w, ts, lane, L);
             dma_state(lds.s0[cl % 3], sbase + (size_t)cl * N * N, 4 * w, 4 * w + 4, lane);
+            if (STATE && p.d_state_T) dma_state(lds.s0[nchunk % 3], p.d_state_T + (size_t)blockIdx.x * N * N, 4 * w, 4 * w + 4, lane);
             vmem_drain();
         }
         block_sync_lds();
@@ -338,6 +349,13 @@ __global__ __launch_bounds__(768) void bwd6_kernel_v2(Bwd6Args p) {
         f32x4 dS1[4];                                       // dS1[jb][r] = dS[i][j = tix(jb, 4g+r)]
 #pragma unroll
         for (int x = 0; x < 4; ++x) dS1[x] = zero4();
+        if (STATE && p.d_state_T) {
+            const float* dT = lds.s0[nchunk % 3];
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) dS1[x][r4] = dT[f32_off(tix(x, 4 * g + r4), 16 * w + c16)];
+        }
         for (int n = 0; n < nsteps; ++n) {
             const int ci = nchunk - n;
             if (ci >= 0 && ci <= nchunk - 1) {
@@ -386,6 +404,13 @@ __global__ __launch_bounds__(768) void bwd6_kernel_v2(Bwd6Args p) {
     f32x4 dS2[4];                                           // dS2[ib][r] = dS[i = tix(ib, 4g+r)][j]
 #pragma unroll
     for (int x = 0; x < 4; ++x) dS2[x] = zero4();
+    if (STATE && p.d_state_T) {
+#pragma unroll
+        for (int ib = 0; ib < 4; ++ib) {
+            const float4 x = *reinterpret_cast<const float4*>(&lds.s0[nchunk % 3][f32_off(j, tix(ib, 4 * g))]);
+            dS2[ib][0] = x.x; dS2[ib][1] = x.y; dS2[ib][2] = x.z; dS2[ib][3] = x.w;
+        }
+    }
     f32x4 dRe = zero4(), dKb = zero4(), dRa = zero4(), dKh = zero4();      // results of a step: written to `res` at the top of the next one
     for (int n = 0; n < nsteps; ++n) {
         const int ci = nchunk - n;
@@ -465,6 +490,12 @@ __global__ __launch_bounds__(768) void bwd6_kernel_v2(Bwd6Args p) {
             }
         }
         block_sync_lds();
+    }
+    if (STATE && p.d_state0) {                              // dL/dS before the first token
+        float* d0 = p.d_state0 + (size_t)blockIdx.x * N * N + (size_t)j * N;
+#pragma unroll
+        for (int ib = 0; ib < 4; ++ib)
+            *reinterpret_cast<float4*>(d0 + tix(ib, 4 * g)) = make_float4(dS2[ib][0], dS2[ib][1], dS2[ib][2], dS2[ib][3]);
     }
 }
 

@@ -48,6 +48,8 @@ struct Fwd6Args {
     const uint16_t* u;              // bf16 (H*N)
     uint16_t* y;                    // bf16 (B,T,H*N)
     float* s;                       // optional f32 (B*H, ceil(T/16), N, N): S^T at the START of every chunk (for the backward)
+    const float* state0;            // STATE only: optional f32 (B*H, N, N) [key j][value i]: the state before token 0 (null = zeros)
+    float* state_T;                 // STATE only: optional f32 (B*H, N, N) [key j][value i]: the state after token T-1 (null = not wanted)
 };
 
 struct Buf6F {
@@ -102,6 +104,11 @@ DEVFN f32x4 score6(const uint16_t (*Xh)[TJ], const uint16_t (*Xl)[TJ], const uin
     return acc;
 }
 
+// STATE (vrwkv_wkv6_forward_state_bf16): S starts from state0[b,h] instead of zeros and is written to state_T[b,h] after the chunk loop -- the
+// padded tokens of a ragged last chunk leave it untouched (k = v = 0, decay 1), so that is the state after exactly T tokens.  Both are the
+// checkpoints' layout ([j][i], this lane's tile addressing), and the checkpoint of chunk 0 then holds state0: the backward needs no extra pointer.
+// With STATE off both `if (STATE ...)` fold away.
+template <bool STATE = false>
 __global__ __launch_bounds__(256) void fwd6_kernel(Fwd6Args p) {
     __shared__ __attribute__((aligned(16))) Lds6F lds;
     const int T = p.T, H = p.H;
@@ -129,6 +136,13 @@ __global__ __launch_bounds__(256) void fwd6_kernel(Fwd6Args p) {
     f32x4 S[4];                           // S^T tiles: S[jb][r] = S^T[j = 16jb+4g+r][i = 16*wave + c16]
 #pragma unroll
     for (int jb = 0; jb < 4; ++jb) S[jb] = zero4();
+    if (STATE && p.state0) {
+        const float* s0 = p.state0 + (size_t)blockIdx.x * N * N + 16 * wave + c16;
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) S[jb][r] = s0[(size_t)(16 * jb + 4 * g + r) * N];
+    }
     float* sdst = p.s ? p.s + ((size_t)blockIdx.x * nchunk * N) * N + 16 * wave + c16 : nullptr;
 
     Raw6 rc;
@@ -210,6 +224,13 @@ __global__ __launch_bounds__(256) void fwd6_kernel(Fwd6Args p) {
             S[jb] = mfma_16x16x32_bf16(mk8(ld8(&B.kbT[0][j][4 * g]), ld8(&B.kbT[1][j][4 * g])), bvv, acc);
         }
     }
+    if (STATE && p.state_T) {
+        float* sT = p.state_T + (size_t)blockIdx.x * N * N + 16 * wave + c16;
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sT[(size_t)(16 * jb + 4 * g + r) * N] = S[jb][r];
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -234,6 +255,8 @@ struct Bwd6Args {
     const float* s;                 // chunk-start checkpoints written by the forward
     uint16_t *gr, *gk, *gv, *gw;    // bf16 (B,T,H*N)
     uint16_t* gu;                   // bf16 (B,H*N): per-sample, summed over the batch by the caller (src/model.py:84)
+    const float* d_state_T;         // STATE only: optional f32 (B*H, N, N) [key j][value i]: dL/d(state after token T-1) (null = zeros)
+    float* d_state0;                // STATE only: optional f32 (B*H, N, N) [key j][value i]: dL/d(state before token 0) (null = not wanted)
 };
 
 constexpr int RS6 = 68;             // row stride (floats) of the tail bounce strips (conflict-free for the float4 column reads)
@@ -271,6 +294,12 @@ DEVFN f32x4 mm_reg_img(f32x4 acc, f32x4 pt, const uint16_t (*Qh)[JT], const uint
     return mfma_16x16x32_bf16(mk8(pl.x, pl.y, 0u, 0u), mk8(qh.x, qh.y, 0u, 0u), acc);
 }
 
+// STATE (vrwkv_wkv6_backward_state_bf16): both copies of dL/dS start from d_state_T[b,h] instead of zeros, each in its own tile orientation, and
+// d_state0[b,h] is dL/dS after chunk 0's update, written from the [i][j] copy dS2 (16 bytes per lane; the two copies are the same sums in a
+// different MFMA order and need not agree to the last bit).  S0 of chunk 0 is the forward's checkpoint 0, i.e. state0, and nothing in the
+// chunk step assumes it to be zero: the decay-gradient term sum_i dS S0 c_L of chunk 0 sees it like any other chunk's.
+// With STATE off both `if (STATE ...)` fold away.
+template <bool STATE = false>
 __global__ __launch_bounds__(256) void bwd6_kernel(Bwd6Args p) {
     __shared__ __attribute__((aligned(16))) Lds6B lds;
     const int T = p.T, H = p.H;
@@ -289,6 +318,16 @@ __global__ __launch_bounds__(256) void bwd6_kernel(Bwd6Args p) {
     f32x4 dS1[4], dS2[4];                           // dS^T[j = 16jb+4g+r][i = 16w+c16] ;  dS[i = 16ib+4g+r][j = 16w+c16]
 #pragma unroll
     for (int x = 0; x < 4; ++x) { dS1[x] = zero4(); dS2[x] = zero4(); }
+    if (STATE && p.d_state_T) {
+        const float* dT = p.d_state_T + (size_t)blockIdx.x * N * N;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) dS1[x][r4] = dT[(size_t)(16 * x + 4 * g + r4) * N + jc];      // [j][i = jc]
+            const float4 t = *reinterpret_cast<const float4*>(dT + (size_t)jc * N + 16 * x + 4 * g);     // [j = jc][i]
+            dS2[x][0] = t.x; dS2[x][1] = t.y; dS2[x][2] = t.z; dS2[x][3] = t.w;
+        }
+    }
     float gu_acc[4] = {0.f, 0.f, 0.f, 0.f};
 
     for (int c = nchunk - 1; c >= 0; --c) {
@@ -467,6 +506,12 @@ __global__ __launch_bounds__(256) void bwd6_kernel(Bwd6Args p) {
             }
         }
         block_sync_lds();               // the next chunk's images overwrite this one's
+    }
+    if (STATE && p.d_state0) {          // dL/dS before the first token
+        float* d0 = p.d_state0 + (size_t)blockIdx.x * N * N + (size_t)jc * N + 4 * g;
+#pragma unroll
+        for (int ib = 0; ib < 4; ++ib)
+            *reinterpret_cast<float4*>(d0 + 16 * ib) = make_float4(dS2[ib][0], dS2[ib][1], dS2[ib][2], dS2[ib][3]);
     }
     // gu[b, h, j] = sum over the tokens of this sample
 #pragma unroll

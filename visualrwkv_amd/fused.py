@@ -1340,10 +1340,16 @@ def supported6(x, m=None):
     return ok
 
 
-def tmix6_forward(m, x, wkv=None):
+_NO_STATE = object()
+
+
+def tmix6_forward(m, x, wkv=None, state=_NO_STATE, want_state=True):
     """RWKV_Tmix_x060.forward (VisualRWKV-v6/v6.0/src/model.py:146-194) with the glue fused: one kernel for the first lerp
     (xxx), one for the five data-dependent lerps, the T,N input-gradient layout for the projections, GroupNorm * silu(gate)
-    in one pass.  `m` is the module (parameter names as in the reference)."""
+    in one pass.  `m` is the module (parameter names as in the reference).  With `state` given (a (B,H,64,64) f32 [key][value]
+    tensor, or None for zeros) this is RWKV_Tmix_x060_state.forward of v6.xx (model.py:137-144): the WKV starts from it and
+    (out, final state) is returned; `wkv` then has RUN_CUDA_RWKV6_STATE's signature, and want_state=False (product op only)
+    leaves the final state unwritten and returns None for it."""
     from . import wkv6 as _wkv6
     B, T, C = x.shape
     mm_ = lora_mm if torch.is_grad_enabled() and LORA_WGRAD else torch.matmul
@@ -1356,10 +1362,16 @@ def tmix6_forward(m, x, wkv=None):
     v = linear(m.value, xv)
     gg = linear(m.gate, xg)
     w = m.time_decay + mm_(torch.tanh(mm_(xw, m.time_decay_w1)), m.time_decay_w2)
-    run = wkv if wkv is not None else _wkv6.RUN_CUDA_RWKV6
-    y = run(B, T, C, m.n_head, r, k, v, w, m.time_faaaa)
+    if state is _NO_STATE:
+        run = wkv if wkv is not None else _wkv6.RUN_CUDA_RWKV6
+        y = run(B, T, C, m.n_head, r, k, v, w, m.time_faaaa)
+    elif wkv is not None:
+        y, state = wkv(B, T, C, m.n_head, r, k, v, w, m.time_faaaa, state)
+    else:
+        y, state = _wkv6.RUN_CUDA_RWKV6_STATE(B, T, C, m.n_head, r, k, v, w, m.time_faaaa, state, want_state)
     y = gn_silu(y.reshape(B * T, C), gg.reshape(B * T, C), m.ln_x.weight, m.ln_x.bias, m.ln_x.eps).view(B, T, C)
-    return linear(m.output, y)
+    out = linear(m.output, y)
+    return out if state is _NO_STATE else (out, state)
 
 
 def cmix6_forward(m, x):
@@ -1386,6 +1398,34 @@ def blocks6_forward(rwkv, x, wkv=None, grad_cp=False):
         else:
             x, delta = seg(block, x, delta)
     _, h = add_ln(x, delta, rwkv.ln_out)
+    return h
+
+
+def blocks6_forward_state(rwkv, x, x_emb, wkv=None, grad_cp=False):
+    """The Block loop of v6.xx's unidirectional_forward + ln_out (VisualRWKV-v6/v6.xx/src/model.py:326-341) on the fused glue: the
+    (x, delta) residual stream is carried twice per Block -- first over the projected image features `x_emb` from a zero WKV state,
+    keeping the state that pass ends in, then over the text `x` from that state (its own final state is not requested).  ln0 of
+    Block 0 applies to both streams (the reference's Block applies it on every call); ln_out runs on the text only.  grad_cp
+    checkpoints the two passes of a Block separately, as model.py:334-336 does."""
+    ln0 = rwkv.blocks[0].ln0
+    x, e = ln0(x), ln0(x_emb)
+    dx = de = None
+
+    def seg(block, x, delta, state, want_state):
+        x, h = add_ln(x, delta, block.ln1)
+        a, state = tmix6_forward(block.att, h, wkv, state=state, want_state=want_state)
+        x, h = add_ln(x, a, block.ln2)
+        return x, cmix6_forward(block.ffn, h), state
+
+    for block in rwkv.blocks:
+        if grad_cp:
+            from torch.utils.checkpoint import checkpoint
+            e, de, state = checkpoint(seg, block, e, de, None, True, use_reentrant=False)
+            x, dx, _ = checkpoint(seg, block, x, dx, state, False, use_reentrant=False)
+        else:
+            e, de, state = seg(block, e, de, None, True)
+            x, dx, _ = seg(block, x, dx, state, False)
+    _, h = add_ln(x, dx, rwkv.ln_out)
     return h
 
 

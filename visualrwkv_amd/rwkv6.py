@@ -92,6 +92,23 @@ class RWKV_Tmix_x060(nn.Module):
         y = self.ln_x(y.view(B * T, C)).view(B, T, C)
         return self.output(y * g)
 
+    def forward_state(self, x, state, wkv=None, want_state=True):
+        """RWKV_Tmix_x060_state.forward of VisualRWKV-v6/v6.xx/src/model.py:137-144 (same parameters as `forward`): the WKV starts
+        from `state` ((B,H,64,64) f32 [key][value]; None = zeros) and the state it ends in is returned.  `wkv`: a callable with
+        RUN_CUDA_RWKV6_STATE's signature.  want_state=False (product op only) leaves the final state unwritten and returns None."""
+        B, T, C = x.size()
+        if getattr(self.args, "fused", False):
+            from . import fused
+            if fused.supported6(x, self) and self.receptance.weight.dtype == torch.bfloat16:
+                return fused.tmix6_forward(self, x, wkv, state=state, want_state=want_state)
+        r, k, v, g, w = self.mix(x)
+        if wkv is not None:
+            y, state = wkv(B, T, C, self.n_head, r, k, v, w, self.time_faaaa, state)
+        else:
+            y, state = _wkv6.RUN_CUDA_RWKV6_STATE(B, T, C, self.n_head, r, k, v, w, self.time_faaaa, state, want_state)
+        y = self.ln_x(y.view(B * T, C)).view(B, T, C)
+        return self.output(y * g), state
+
 
 class RWKV_CMix_x060(nn.Module):
     """RWKV-6 channel-mix with the receptance gate (model.py:198-226)."""
@@ -152,6 +169,15 @@ class Block(nn.Module):
         x = x + self.ffn(self.ln2(x))
         return x
 
+    def forward_state(self, x, state, wkv=None, want_state=True):
+        """Block.forward of v6.xx (model.py:202-210): -> (x, state)."""
+        if self.layer_id == 0:
+            x = self.ln0(x)
+        xx, state = self.att.forward_state(self.ln1(x), state, wkv, want_state)
+        x = x + xx
+        x = x + self.ffn(self.ln2(x))
+        return x, state
+
 
 class RWKV(nn.Module):
     """Embedding -> n_layer Blocks -> ln_out -> head (model.py:277-325); same state-dict keys as the reference."""
@@ -182,3 +208,22 @@ class RWKV(nn.Module):
             else:
                 x = block(x, wkv)
         return self.head(self.ln_out(x))
+
+    def forward_state(self, x, x_emb, wkv=None):
+        """The Block loop of v6.xx's unidirectional_forward (model.py:326-343) + ln_out (no head): every Block first runs over the projected
+        image features `x_emb` from a zero state, then over the text `x` from the state that pass ended in.  The image takes no context
+        tokens, and its projector is reached only through dL/dS.  The text pass's own final state is not requested."""
+        args = self.args
+        if getattr(args, "fused", False) and args.dropout == 0:
+            from . import fused
+            if fused.supported6(x) and fused.add_ln_supported(x) and self.head.weight.dtype == torch.bfloat16:
+                return fused.blocks6_forward_state(self, x, x_emb, wkv, grad_cp=args.grad_cp >= 1 and torch.is_grad_enabled())
+        for block in self.blocks:
+            if args.grad_cp >= 1 and torch.is_grad_enabled():      # the two passes of a Block are checkpointed separately (model.py:334-336)
+                from torch.utils.checkpoint import checkpoint
+                x_emb, state = checkpoint(block.forward_state, x_emb, None, wkv, use_reentrant=False)
+                x, _ = checkpoint(block.forward_state, x, state, wkv, False, use_reentrant=False)
+            else:
+                x_emb, state = block.forward_state(x_emb, None, wkv)
+                x, _ = block.forward_state(x, state, wkv, False)
+        return self.ln_out(x)

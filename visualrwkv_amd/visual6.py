@@ -3,7 +3,12 @@
 CLIP ViT-L/14 features (any module returning `.last_hidden_state` with a leading CLS token), `grid_pooling`, a linear
 projector, the image span inserted after the left-padded first text part (`preparing_embedding`), and the
 "bidirectional" pass that flips the image span on odd layers (`bidirectional_forward`).  Loss = the v7 one
-(`training_step`, model.py:441-458 is the same code)."""
+(`training_step`, model.py:441-458 is the same code).
+
+`args.image_state = 1` selects the v6.xx model instead (VisualRWKV-v6/v6.xx/src/model.py:321-343,429-495, "state tuning"): the image is
+not part of the context.  Every Block first runs over the projected image features from a zero WKV state, and the state that pass ends
+in is the initial state of the same Block's pass over the text (`preparing_embedding_state`, `unidirectional_forward`, `generate`).
+The projector is trained only through dL/dS (wkv6.RUN_CUDA_RWKV6_STATE).  The default 0 is the bidirectional model above."""
 from __future__ import annotations
 
 import torch
@@ -42,8 +47,59 @@ class VisualRWKV6(nn.Module):
 
     # ---- model.py:401-427
     def forward(self, samples, wkv=None):
+        if getattr(self.args, "image_state", 0):
+            x, targets, image_features = self.preparing_embedding_state(samples)
+            return self.unidirectional_forward(x, image_features, wkv), targets
         x, targets, _ = self.preparing_embedding(samples)
         return self.bidirectional_forward(x, wkv), targets
+
+    # ---- v6.xx model.py:326-343
+    def unidirectional_forward(self, x, x_emb, wkv=None):
+        """x: the text embeddings (B,T,C); x_emb: the projected image features (B,L,C).  `wkv`: a callable with RUN_CUDA_RWKV6_STATE's
+        signature (tests pass the oracle)."""
+        args = self.args
+        if args.dropout > 0:
+            x = self.rwkv.drop0(x)
+        h = self.rwkv.forward_state(x, x_emb, wkv)
+        if getattr(args, "fused", False) and h.is_cuda and self.rwkv.head.weight.dtype == torch.bfloat16:
+            from . import fused
+            return fused.linear(self.rwkv.head, h)
+        return self.rwkv.head(h)
+
+    def image_states(self, x_emb, wkv=None):
+        """The per-layer WKV states the image pass ends in: [(B,H,64,64) f32] * n_layer."""
+        states = []
+        for block in self.rwkv.blocks:
+            x_emb, state = block.forward_state(x_emb, None, wkv)
+            states.append(state)
+        return states
+
+    def text_forward(self, x, states, wkv=None):
+        """The text pass alone, from the states of `image_states`: the logits `unidirectional_forward` gives."""
+        for block, state in zip(self.rwkv.blocks, states):
+            x, _ = block.forward_state(x, state, wkv, False)
+        return self.rwkv.head(self.rwkv.ln_out(x))
+
+    @torch.no_grad()
+    def generate(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx, wkv=None):
+        """Greedy generation of one sample in image-state mode (v6.xx model.py:468-495, which calls a method that file does not have: this
+        is its intent).  The per-layer image states are computed once; the text pass is re-run from them for every new token (a stateful
+        RWKV-6 decode step is not built)."""
+        if not getattr(self.args, "image_state", 0):
+            raise NotImplementedError("generate is built for args.image_state = 1")
+        if do_sample:
+            raise NotImplementedError
+        samples = {"input_ids": input_ids, "images": images, "labels": torch.full_like(input_ids, IGNORE_INDEX)}
+        x, _, image_features = self.preparing_embedding_state(samples, truncate=False)
+        states = self.image_states(image_features, wkv)
+        generated = []
+        for _ in range(max_new_tokens):
+            next_token = torch.argmax(self.text_forward(x, states, wkv)[:, -1, :], dim=-1, keepdim=True)
+            generated.append(next_token.item())
+            if generated[-1] == stop_token_idx:
+                break
+            x = torch.cat((x, self.rwkv.emb(next_token)), dim=-2)[:, -self.args.ctx_len:, :]
+        return generated
 
     def bidirectional_forward(self, x, wkv=None):
         args = self.args
@@ -134,6 +190,36 @@ class VisualRWKV6(nn.Module):
             new_labels.append(torch.cat((head_lab, torch.full((feats.shape[0],), IGNORE_INDEX, dtype=labels.dtype, device=device),
                                          tail_lab)))
         if truncate:                                   # keep the beginning unless it carries no label (model.py:496-509)
+            L = self.args.ctx_len
+            for i, (x, y) in enumerate(zip(embeds, new_labels)):
+                if bool((y[:L] != IGNORE_INDEX).any()):
+                    embeds[i], new_labels[i] = x[:L], y[:L]
+                else:
+                    embeds[i], new_labels[i] = x[-L:], y[-L:]
+        max_len = max(x.shape[0] for x in embeds)
+        out = torch.zeros(len(embeds), max_len, self.args.n_embd, dtype=samples["images"].dtype, device=device)
+        lab = torch.full((len(embeds), max_len), IGNORE_INDEX, dtype=labels.dtype, device=device)
+        for i, (x, y) in enumerate(zip(embeds, new_labels)):
+            out[i, :x.shape[0]] = x
+            lab[i, :y.shape[0]] = y
+        return out, lab, image_features
+
+    # ---- v6.xx model.py:414-466: the text is what stands right of the image token; the image is returned beside it
+    def preparing_embedding_state(self, samples, truncate=True):
+        ids, labels = samples["input_ids"], samples["labels"]
+        device = labels.device
+        image_features = self.encode_images(samples["images"])
+        n_img = (ids == IMAGE_TOKEN_INDEX).sum(1)
+        if int(n_img.max()) > 1:
+            raise ValueError("Too many images in one sample, should be 0 or 1.")
+        # a sample without an image gets zeroed features
+        image_features = torch.where((n_img == 1).view(-1, 1, 1), image_features, torch.zeros_like(image_features))
+        embeds, new_labels = [], []
+        for b in range(ids.shape[0]):
+            start = int((ids[b] == IMAGE_TOKEN_INDEX).int().argmax()) + 1 if int(n_img[b]) == 1 else 0
+            embeds.append(self.rwkv.emb(ids[b, start:]))
+            new_labels.append(labels[b, start:])
+        if truncate:                                   # truncate_input: keep the beginning unless it carries no label
             L = self.args.ctx_len
             for i, (x, y) in enumerate(zip(embeds, new_labels)):
                 if bool((y[:L] != IGNORE_INDEX).any()):

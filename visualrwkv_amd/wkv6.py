@@ -6,6 +6,11 @@ Mirrors VisualRWKV-v6/v6.0/src/model.py:38-88: the extension module's `forward` 
 Differences a caller cannot see: the forward also writes chunk-start state checkpoints that `WKV_6` keeps for the
 backward (the reference re-sweeps the sequence five times instead), and T has no compile-time bound (the reference
 sizes a per-thread array with -D_T_=ctx_len).  CPU tensors raise: there is no CPU implementation, as in the reference.
+
+`WKV_6_STATE` / `RUN_CUDA_RWKV6_STATE(B, T, C, H, r, k, v, w, u, s) -> (x, state)` mirror VisualRWKV-v6/v6.xx/src/model.py:35-42 (there a
+wrapper over fla's fused_recurrent_rwkv6 with initial_state / output_final_state): the same kernels started from a (B,H,64,64) fp32
+[key][value] state, returning the state after the last token, differentiable through both (vrwkv_wkv6_forward_state_bf16 /
+vrwkv_wkv6_backward_state_bf16).  All launches go through the state entries; with no state given they run the plain kernels.
 """
 from __future__ import annotations
 
@@ -58,8 +63,15 @@ def _timed(kind, elems, dev, fn):
     return rc
 
 
-def forward_hip(B, T, C, H, r, k, v, ew, u, y, ckpt=None):
-    """ew is the f32 log decay the reference's kernels take (`w` of wkv6_op.cpp:8)."""
+def _chk_state(name, t, B, H):
+    if t is not None:
+        _chk(name, t, (B, H, HEAD_SIZE, HEAD_SIZE), torch.float32)
+    return t.data_ptr() if t is not None else 0
+
+
+def forward_hip(B, T, C, H, r, k, v, ew, u, y, ckpt=None, state0=None, state_T=None):
+    """ew is the f32 log decay the reference's kernels take (`w` of wkv6_op.cpp:8).  state0 / state_T: optional (B,H,64,64) f32
+    [key][value] states before token 0 / after token T-1 (None: zeros / not wanted; with both None the state entry IS the plain one)."""
     bf = torch.bfloat16
     for n, t in (("r", r), ("k", k), ("v", v), ("y", y)):
         _chk(n, t, (B, T, C), bf)
@@ -67,13 +79,17 @@ def forward_hip(B, T, C, H, r, k, v, ew, u, y, ckpt=None):
     if u.numel() != C:
         raise ValueError(f"wkv6: u must have {C} elements")
     _chk("u", u, u.shape, bf)
+    s0, sT = _chk_state("state0", state0, B, H), _chk_state("state_T", state_T, B, H)
     with torch.cuda.device(r.device):
-        rc = _timed("fwd", B * T * C, r.device, lambda: hip_lib.load().vrwkv_wkv6_forward_bf16(
-            B, T, C, H, r.data_ptr(), k.data_ptr(), v.data_ptr(), ew.data_ptr(), u.data_ptr(), y.data_ptr(), ckpt.data_ptr() if ckpt is not None else 0, _stream(r)))
-    hip_lib.check(rc, "vrwkv_wkv6_forward_bf16")
+        rc = _timed("fwd", B * T * C, r.device, lambda: hip_lib.load().vrwkv_wkv6_forward_state_bf16(
+            B, T, C, H, r.data_ptr(), k.data_ptr(), v.data_ptr(), ew.data_ptr(), u.data_ptr(), s0, y.data_ptr(), sT,
+            ckpt.data_ptr() if ckpt is not None else 0, _stream(r)))
+    hip_lib.check(rc, "vrwkv_wkv6_forward_state_bf16")
 
 
-def backward_hip(B, T, C, H, r, k, v, ew, u, gy, gr, gk, gv, gw, gu, ckpt=None):
+def backward_hip(B, T, C, H, r, k, v, ew, u, gy, gr, gk, gv, gw, gu, ckpt=None, state0=None, d_state_T=None, d_state0=None):
+    """d_state_T / d_state0: optional (B,H,64,64) f32 gradients of the state after the last / before the first token (None: zeros / not
+    wanted).  state0 is read only when the checkpoints are regenerated here: a saved `ckpt` already starts from it."""
     bf = torch.bfloat16
     for n, t in (("r", r), ("k", k), ("v", v), ("gy", gy), ("gr", gr), ("gk", gk), ("gv", gv), ("gw", gw)):
         _chk(n, t, (B, T, C), bf)
@@ -82,12 +98,13 @@ def backward_hip(B, T, C, H, r, k, v, ew, u, gy, gr, gk, gv, gw, gu, ckpt=None):
     _chk("gu", gu, (B, C), bf)
     if ckpt is None:            # reference calling convention: no saved state -> regenerate the checkpoints
         ckpt = ckpt_tensor(B, T, H, r.device)
-        forward_hip(B, T, C, H, r, k, v, ew, u, torch.empty_like(r), ckpt)
+        forward_hip(B, T, C, H, r, k, v, ew, u, torch.empty_like(r), ckpt, state0)
+    dT, d0 = _chk_state("d_state_T", d_state_T, B, H), _chk_state("d_state0", d_state0, B, H)
     with torch.cuda.device(r.device):
-        rc = _timed("bwd", B * T * C, r.device, lambda: hip_lib.load().vrwkv_wkv6_backward_bf16(
-            B, T, C, H, r.data_ptr(), k.data_ptr(), v.data_ptr(), ew.data_ptr(), u.data_ptr(), gy.data_ptr(), ckpt.data_ptr(), gr.data_ptr(),
-            gk.data_ptr(), gv.data_ptr(), gw.data_ptr(), gu.data_ptr(), _stream(r)))
-    hip_lib.check(rc, "vrwkv_wkv6_backward_bf16")
+        rc = _timed("bwd", B * T * C, r.device, lambda: hip_lib.load().vrwkv_wkv6_backward_state_bf16(
+            B, T, C, H, r.data_ptr(), k.data_ptr(), v.data_ptr(), ew.data_ptr(), u.data_ptr(), gy.data_ptr(), ckpt.data_ptr(), dT, gr.data_ptr(),
+            gk.data_ptr(), gv.data_ptr(), gw.data_ptr(), gu.data_ptr(), d0, _stream(r)))
+    hip_lib.check(rc, "vrwkv_wkv6_backward_state_bf16")
 
 
 def _apply_variant_env():
@@ -149,3 +166,48 @@ class WKV_6(torch.autograd.Function):
 
 def RUN_CUDA_RWKV6(B, T, C, H, r, k, v, w, u):
     return WKV_6.apply(B, T, C, H, r, k, v, w, u)
+
+
+class WKV_6_STATE(torch.autograd.Function):
+    """WKV_6 with a carried state: what RUN_CUDA_RWKV6_STATE of VisualRWKV-v6/v6.xx/src/model.py:35-42 computes through fla's
+    fused_recurrent_rwkv6(initial_state=, output_final_state=True), forward and backward.  `s`: (B,H,64,64) f32 [key][value] or None (zeros).
+    Returns (y bf16, state f32 or None with want_state=False).  dL/ds is produced only when `s` needs it; dL/d(state) enters only when the returned state got a gradient."""
+
+    @staticmethod
+    def forward(ctx, B, T, C, H, r, k, v, w, u, s, want_state=True):
+        with torch.no_grad():
+            assert all(x.dtype == torch.bfloat16 for x in (r, k, v, w, u))
+            assert HEAD_SIZE == C // H
+            assert all(x.is_contiguous() for x in (r, k, v, w, u))
+            ctx.B, ctx.T, ctx.C, ctx.H = B, T, C, H
+            ctx.set_materialize_grads(False)
+            ew = (-torch.exp(w.float())).contiguous()
+            y = torch.empty((B, T, C), device=r.device, dtype=torch.bfloat16)
+            state = torch.empty((B, H, HEAD_SIZE, HEAD_SIZE), device=r.device, dtype=torch.float32) if want_state else None
+            ckpt = ckpt_tensor(B, T, H, r.device) if any(ctx.needs_input_grad) else None
+            forward_hip(B, T, C, H, r, k, v, ew, u, y, ckpt, s.contiguous() if s is not None else None, state)
+            ctx.save_for_backward(r, k, v, ew, u, ckpt)          # the checkpoint of chunk 0 holds s
+            return y, state
+
+    @staticmethod
+    def backward(ctx, gy, gstate):
+        with torch.no_grad():
+            B, T, C, H = ctx.B, ctx.T, ctx.C, ctx.H
+            r, k, v, ew, u, ckpt = ctx.saved_tensors
+            if gy is None:
+                gy = torch.zeros((B, T, C), device=r.device, dtype=torch.bfloat16)
+            assert gy.dtype == torch.bfloat16
+            gy = gy.contiguous()
+            gr, gk, gv, gw = (torch.empty((B, T, C), device=gy.device, dtype=torch.bfloat16) for _ in range(4))
+            gu = torch.empty((B, C), device=gy.device, dtype=torch.bfloat16)
+            gs = torch.empty((B, H, HEAD_SIZE, HEAD_SIZE), device=gy.device, dtype=torch.float32) if ctx.needs_input_grad[9] else None
+            backward_hip(B, T, C, H, r, k, v, ew, u, gy, gr, gk, gv, gw, gu, ckpt,
+                         d_state_T=gstate.float().contiguous() if gstate is not None else None, d_state0=gs)
+            gu = gu.float().sum(0).view(H, C // H).to(u.dtype)         # per-sample bf16 rows, summed in fp32
+            return (None, None, None, None, gr, gk, gv, gw, gu, gs, None)
+
+
+def RUN_CUDA_RWKV6_STATE(B, T, C, H, r, k, v, w, u, s, want_state=True):
+    """-> (x, state): VisualRWKV-v6/v6.xx/src/model.py:35-42.  want_state=False (not in the reference): the final state is not written and
+    None is returned for it."""
+    return WKV_6_STATE.apply(B, T, C, H, r, k, v, w, u, s, want_state)
