@@ -106,10 +106,13 @@ class Backend:
     def gen(self, seed):
         return torch.Generator(device=self.dev).manual_seed(seed)
 
-    def call(self, fn, argtypes, *args):
+    def rc(self, fn, argtypes, *args):
         f = getattr(self.lib, fn)
         f.argtypes, f.restype = argtypes + [VP], I
-        rc = f(*args, self.stream)
+        return f(*args, self.stream)
+
+    def call(self, fn, argtypes, *args):
+        rc = self.rc(fn, argtypes, *args)
         assert rc == 0, (fn, rc)
 
     def ws_floats(self, ntok, C, nvec):
@@ -457,3 +460,232 @@ def test_gn_silu(backend, be, sid):
     act(be, r1["dgg"], xs[1].grad, f"{tag} dgg")
     for j, name in enumerate(("dln_w", "dln_b")):
         par(be, r1["dparams"][j], xs[2 + j].grad, f"{tag} {name}")
+
+
+# ------------------------------------------------------------------------------------------------ refusals, forwarding entries
+EINVAL, ESHAPE = -1, -2                                   # VRWKV_EINVAL, VRWKV_ESHAPE of include/visualrwkv_hip.h
+# Every vrwkv_* entry of tmix_fused.hip that returns a code (vrwkv_param_grad_ws_floats returns a size), its arguments in order:
+# ntok T C M has eps n are the scalars; a name is a required pointer, name? an optional one (NULL in the valid call), name* one that
+# has_vres requires, name[] an array of pointers (M of them, 5 for ddmix); > marks what the entry writes.
+GLUE_ENTRIES = {
+    "vrwkv_mix_fwd_bf16": "ntok T C M x mu[] >out[]",
+    "vrwkv_mix_fwd_prev_bf16": "ntok T C M x x_prev? mu[] >out[]",
+    "vrwkv_mix_bwd_bf16": "ntok T C M x mu[] dout[] >dx >dmu >ws",
+    "vrwkv_mix_bwd2_bf16": "ntok T C M x mu[] dout[] dout3_second? >dx >dmu >ws",
+    "vrwkv_mix_bwd_ln_bf16": "ntok T C M xn mean rstd ln_w ln_b mu[] dout[] dout3_second? >dx >dmu >ws",
+    "vrwkv_mix_bwd_ln_packed_bf16": "ntok T C M xn mean rstd ln_w ln_b mu[] dout[] dout3_second? first? >dx >dmu >ws",
+    "vrwkv_mix_bwd_ln_carry_bf16": "ntok T C M xn mean rstd ln_w ln_b mu[] dout[] dout3_second? y_prev? dy_last? >dy_prev? >dx >dmu >ws",
+    "vrwkv_ddmix_fwd_bf16": "ntok T C x mu[] mm[] >out[]",
+    "vrwkv_ddmix_bwd_bf16": "ntok T C x mu[] mm[] dout[] >dx >dmm[] >dmu >ws",
+    "vrwkv_gn_silu_fwd_bf16": "ntok C eps y gg ln_w ln_b >out",
+    "vrwkv_gn_silu_bwd_bf16": "ntok C eps y gg ln_w ln_b dout >dy >dgg >dparams >ws",
+    "vrwkv_decay_fwd_bf16": "ntok C h w0 >w",
+    "vrwkv_decay_bwd_bf16": "ntok C h w0 dw >dh >dw0 >ws",
+    "vrwkv_kva_fwd_bf16": "ntok C has k v* vfirst* vl* al k_k k_a a0 v0* >k2 >v2* >z >b",
+    "vrwkv_kva_bwd_bf16": "ntok C has k v* vfirst* vl* al k_k k_a a0 v0* dk2 dv2* dz db >dk >dv* >dvfirst* >dvl* >dal >dparams >ws",
+    "vrwkv_kva_bwd2_bf16": "ntok C has k v* vfirst* vl* al k_k k_a a0 v0* dk2 dv2* dz db dk2_second? dv2_second? "
+                           ">dk >dv* >dvfirst* >dvl* >dal >dparams >ws",
+    "vrwkv_kva_bwd3_bf16": "ntok C has k v* vfirst* vl* al k_k k_a a0 v0* dk2 dv2* dz db dk2_second? dv2_second? dvfirst_in? "
+                           ">dk >dv* >dvfirst* >dvl* >dal >dparams >ws",
+    "vrwkv_post_fwd_bf16": "ntok C eps y r k v g ln_w ln_b r_k >out",
+    "vrwkv_post_bwd_bf16": "ntok C eps y r k v g ln_w ln_b r_k dout >dy >dr >dk >dv >dg >dparams >ws",
+    "vrwkv_relusq_fwd_bf16": "n h >y",
+    "vrwkv_relusq_bwd_bf16": "n h dy >dh",
+}
+SCALARS = {"ntok": L, "T": I, "C": I, "M": I, "has": I, "eps": F32, "n": L}
+VALID = {"ntok": 4, "T": 2, "C": 64, "M": 6, "has": 1, "eps": EPS, "n": 4 * 64}
+REFUSE_BUF = 8 * 8256                  # floats per buffer: 4 rows (5 in `ragged`) of the widest C tried, 6 partial rows -- no case depends on being refused to stay in bounds
+
+
+def _defects(sig):
+    """The defective calls of one entry: {id: {argument: value}}, a pointer's value None (NULL) or, for an optional one, True (given);
+    (array, i) addresses one element.  One defect each, then the pairs that show which check comes first."""
+    args = sig.split()
+    names = [a.strip(">?*[]") for a in args]
+    required = [n for a, n in zip(args, names) if n not in SCALARS and not a.endswith("?")]
+    arrays = [n for a, n in zip(args, names) if a.endswith("[]")]
+    last = 4 if "M" not in names else 5
+    novres = {"has": 0, **{n: None for a, n in zip(args, names) if a.endswith("*")}}
+    d = {}
+    if "ntok" in names:
+        d["ntok0"] = {"ntok": 0}
+    if "T" in names:
+        d["T0"] = {"T": 0}
+        d["ragged"] = {"ntok": 5}                          # ntok % T != 0
+    if "C" in names:
+        d.update({f"C{c}": {"C": c} for c in (0, 32, 8256)})
+        d[f"C32+null:{required[0]}"] = {"C": 32, required[0]: None}
+    d.update({f"null:{n}": {n: None} for n in required})
+    for n in arrays:
+        d[f"null:{n}[{last}]"] = {(n, last): None}
+        d[f"C32+null:{n}[{last}]"] = {"C": 32, (n, last): None}
+    if "M" in names:
+        d["M3"] = {"M": 3}
+    if "M" in names and "dout3_second" in names:
+        d["M1+dout3_second"] = {"M": 1, "dout3_second": True}
+    for opt in ("dv2_second", "dvfirst_in"):
+        if opt in names:
+            d[f"novres+{opt}"] = {**novres, opt: True}
+    if "dv2_second" in names:
+        d["ntok0+novres+dv2_second"] = {**novres, "ntok": 0, "dv2_second": True}
+    # `first` together with y_prev in mix_bwd_ln (tmix_fused.hip) is EINVAL there, but no exported entry takes both: nothing to call
+    if "n" in names:
+        d["n0"] = {"n": 0}
+        d["n%8"] = {"n": 4 * 64 + 4}
+    return d
+
+
+# What every entry answered before its host side was folded into one check / launch path, read off that code by running these very
+# calls against it (not derived from what the codes ought to be).  NULL, a count of zero and a bad M are found before a bad shape,
+# except the elements of a pointer array, which the mix and ddmix entries look at after the shape.
+_MIX_ESHAPE = "ragged C0 C32 C8256 C32+null:mu[5] "
+_MIX_LN_EINVAL = ("ntok0 T0 C32+null:xn null:xn null:mean null:rstd null:ln_w null:ln_b null:mu null:dout null:dx null:dmu null:ws "
+                  "null:mu[5] null:dout[5] M3 M1+dout3_second")
+_KVA_BWD_EINVAL = ("ntok0 C32+null:k null:k null:v null:vfirst null:vl null:al null:k_k null:k_a null:a0 null:v0 null:dk2 null:dv2 null:dz "
+                   "null:db null:dk null:dv null:dvfirst null:dvl null:dal null:dparams null:ws ")
+_ROW_ESHAPE = "C0 C32 C8256"
+REFUSALS = {
+    "vrwkv_mix_fwd_bf16": {EINVAL: "ntok0 T0 C32+null:x null:x null:mu null:out null:mu[5] null:out[5] M3",
+                           ESHAPE: _MIX_ESHAPE + "C32+null:out[5]"},
+    "vrwkv_mix_fwd_prev_bf16": {EINVAL: "ntok0 T0 C32+null:x null:x null:mu null:out null:mu[5] null:out[5] M3",
+                                ESHAPE: _MIX_ESHAPE + "C32+null:out[5]"},
+    "vrwkv_mix_bwd_bf16": {EINVAL: "ntok0 T0 C32+null:x null:x null:mu null:dout null:dx null:dmu null:ws null:mu[5] null:dout[5] M3",
+                           ESHAPE: _MIX_ESHAPE + "C32+null:dout[5]"},
+    "vrwkv_mix_bwd2_bf16": {EINVAL: "ntok0 T0 C32+null:x null:x null:mu null:dout null:dx null:dmu null:ws null:mu[5] null:dout[5] M3 "
+                                    "M1+dout3_second",
+                            ESHAPE: _MIX_ESHAPE + "C32+null:dout[5]"},
+    "vrwkv_mix_bwd_ln_bf16": {EINVAL: _MIX_LN_EINVAL, ESHAPE: _MIX_ESHAPE + "C32+null:dout[5]"},
+    "vrwkv_mix_bwd_ln_packed_bf16": {EINVAL: _MIX_LN_EINVAL, ESHAPE: _MIX_ESHAPE + "C32+null:dout[5]"},
+    "vrwkv_mix_bwd_ln_carry_bf16": {EINVAL: _MIX_LN_EINVAL, ESHAPE: _MIX_ESHAPE + "C32+null:dout[5]"},
+    "vrwkv_ddmix_fwd_bf16": {EINVAL: "ntok0 T0 C32+null:x null:x null:mu null:mm null:out null:mu[4] null:mm[4] null:out[4]",
+                             ESHAPE: "ragged C0 C32 C8256 C32+null:mu[4] C32+null:mm[4] C32+null:out[4]"},
+    "vrwkv_ddmix_bwd_bf16": {EINVAL: "ntok0 T0 C32+null:x null:x null:mu null:mm null:dout null:dx null:dmm null:dmu null:ws null:mu[4] "
+                                     "null:mm[4] null:dout[4] null:dmm[4]",
+                             ESHAPE: "ragged C0 C32 C8256 C32+null:mu[4] C32+null:mm[4] C32+null:dout[4] C32+null:dmm[4]"},
+    "vrwkv_gn_silu_fwd_bf16": {EINVAL: "ntok0 C32+null:y null:y null:gg null:ln_w null:ln_b null:out", ESHAPE: _ROW_ESHAPE},
+    "vrwkv_gn_silu_bwd_bf16": {EINVAL: "ntok0 C32+null:y null:y null:gg null:ln_w null:ln_b null:dout null:dy null:dgg null:dparams null:ws",
+                               ESHAPE: _ROW_ESHAPE},
+    "vrwkv_decay_fwd_bf16": {EINVAL: "ntok0 C32+null:h null:h null:w0 null:w", ESHAPE: _ROW_ESHAPE},
+    "vrwkv_decay_bwd_bf16": {EINVAL: "ntok0 C32+null:h null:h null:w0 null:dw null:dh null:dw0 null:ws", ESHAPE: _ROW_ESHAPE},
+    "vrwkv_kva_fwd_bf16": {EINVAL: "ntok0 C32+null:k null:k null:v null:vfirst null:vl null:al null:k_k null:k_a null:a0 null:v0 null:k2 "
+                                   "null:v2 null:z null:b",
+                           ESHAPE: _ROW_ESHAPE},
+    "vrwkv_kva_bwd_bf16": {EINVAL: _KVA_BWD_EINVAL, ESHAPE: _ROW_ESHAPE},
+    "vrwkv_kva_bwd2_bf16": {EINVAL: _KVA_BWD_EINVAL + "novres+dv2_second ntok0+novres+dv2_second", ESHAPE: _ROW_ESHAPE},
+    "vrwkv_kva_bwd3_bf16": {EINVAL: _KVA_BWD_EINVAL + "novres+dv2_second novres+dvfirst_in ntok0+novres+dv2_second", ESHAPE: _ROW_ESHAPE},
+    "vrwkv_post_fwd_bf16": {EINVAL: "ntok0 C32+null:y null:y null:r null:k null:v null:g null:ln_w null:ln_b null:r_k null:out",
+                            ESHAPE: _ROW_ESHAPE},
+    "vrwkv_post_bwd_bf16": {EINVAL: "ntok0 C32+null:y null:y null:r null:k null:v null:g null:ln_w null:ln_b null:r_k null:dout null:dy "
+                                    "null:dr null:dk null:dv null:dg null:dparams null:ws",
+                            ESHAPE: _ROW_ESHAPE},
+    "vrwkv_relusq_fwd_bf16": {EINVAL: "null:h null:y n0", ESHAPE: "n%8"},
+    "vrwkv_relusq_bwd_bf16": {EINVAL: "null:h null:dy null:dh n0", ESHAPE: "n%8"},
+}
+
+
+def _entry_rc(be, name, zeros, outs, change):
+    """The code of one call of `name`: the VALID scalars, every required pointer given -- `zeros` for what the entry reads, a row of
+    `outs` each for what it writes --, then `change` applied (see _defects)."""
+    vals, types, k = [], [], 0
+    for a in GLUE_ENTRIES[name].split():
+        n = a.strip(">?*[]")
+        if n in SCALARS:
+            vals.append(change.get(n, VALID[n]))
+            types.append(SCALARS[n])
+            continue
+        ptrs = []
+        for i in range(6 if a.endswith("[]") else 1):
+            ptrs.append(outs[k].data_ptr() if a.startswith(">") else zeros.data_ptr())
+            k += a.startswith(">")
+            if (n, i) in change:
+                ptrs[i] = None
+        if not change.get(n, not a.endswith("?")):
+            vals.append(None)
+        else:
+            vals.append((VP * 6)(*ptrs) if a.endswith("[]") else VP(ptrs[0]))
+        types.append(VP)
+    return be.rc(name, types, *vals)
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_glue_entries_refuse_in_order(backend, be):
+    """Every entry answers every defective call of _defects with the code of REFUSALS and launches nothing: what it would write is NaN
+    before the call and after it.  The call without a defect then runs."""
+    zeros = torch.zeros(REFUSE_BUF, dtype=torch.float32, device=be.dev)
+    outs = torch.full((12, REFUSE_BUF), float("nan"), dtype=torch.float32, device=be.dev)
+    assert set(REFUSALS) == set(GLUE_ENTRIES)
+    for name, sig in GLUE_ENTRIES.items():
+        want = {d: code for code, ds in REFUSALS[name].items() for d in ds.split()}
+        defects = _defects(sig)
+        assert set(want) == set(defects), name
+        for did, change in defects.items():
+            rc = _entry_rc(be, name, zeros, outs, change)
+            assert rc == want[did], (name, did, rc)
+            assert bool(torch.isnan(outs).all()), (name, did, "a refused call wrote")
+        assert _entry_rc(be, name, zeros, outs, {}) == 0, name
+        outs.fill_(float("nan"))
+
+
+def _same_results(runs, tag):
+    """Every run's buffers written up to their guard rows and bit for bit those of the first run."""
+    for res in runs:
+        written(res, None, 0)
+    for res in runs[1:]:
+        for name in runs[0]:
+            assert torch.equal(bits(res[name]), bits(runs[0][name])), f"{tag} {name}: the forwarding entry differs from the full one"
+
+
+@pytest.mark.parametrize("backend,sid", [c for c in _cases() if c.values[1] in FULL_MATRIX])
+def test_forwarding_entries_are_the_full_entry(backend, be, sid):
+    """The entries that only forward -- mix_fwd, mix_bwd, kva_bwd, kva_bwd2 -- and the three mix_bwd_ln entries with their optional
+    pointers NULL: bit for bit (outputs and fp32 parameter gradients) the entry they forward to."""
+    B, T, C = be.shape(sid)
+    ntok = B * T
+    g = be.gen(19 * ntok + C)
+    x = rnd(be, g, ntok, C)
+    for M in (1, 2, 6):
+        mus, douts = [unif(be, g, C) for _ in range(M)], [rnd(be, g, ntok, C) for _ in range(M)]
+        runs = []
+        for prev in (False, True):
+            outs = [nan_rows(be, ntok, C) for _ in range(M)]
+            if prev:
+                be.call("vrwkv_mix_fwd_prev_bf16", [L, I, I, I] + [VP] * 4, ntok, T, C, M, P(x), None, PA(mus), PA(outs))
+            else:
+                be.call("vrwkv_mix_fwd_bf16", [L, I, I, I] + [VP] * 3, ntok, T, C, M, P(x), PA(mus), PA(outs))
+            runs.append({f"out{j}": o for j, o in enumerate(outs)})
+        _same_results(runs, f"mix_fwd/{sid}/M{M}")
+        runs = []
+        for full in (False, True):
+            dx, dmu, ws = nan_rows(be, ntok, C), nan_rows(be, M, C, torch.float32), nan_ws(be, ntok, C, M)
+            if full:
+                be.call("vrwkv_mix_bwd2_bf16", [L, I, I, I] + [VP] * 7, ntok, T, C, M, P(x), PA(mus), PA(douts), None, P(dx), P(dmu), P(ws))
+            else:
+                be.call("vrwkv_mix_bwd_bf16", [L, I, I, I] + [VP] * 6, ntok, T, C, M, P(x), PA(mus), PA(douts), P(dx), P(dmu), P(ws))
+            runs.append({"dx": dx, "dmu": dmu})
+        _same_results(runs, f"mix_bwd/{sid}/M{M}")
+
+    # mix_bwd_ln (M = 6), with and without the second gradient of output 3
+    mean, rstd = torch.randn(ntok, generator=g, device=be.dev) * 0.1, torch.rand(ntok, generator=g, device=be.dev) + 0.5
+    ln_w, ln_b = rnd(be, g, C, scale=0.5, shift=1.0), rnd(be, g, C, scale=0.1)
+    for d3b in (None, rnd(be, g, ntok, C)):
+        runs = []
+        for entry, nulls in (("vrwkv_mix_bwd_ln_bf16", 0), ("vrwkv_mix_bwd_ln_packed_bf16", 1), ("vrwkv_mix_bwd_ln_carry_bf16", 3)):
+            dx, dmu, ws = nan_rows(be, ntok, C), nan_rows(be, 6, C, torch.float32), nan_ws(be, ntok, C, 6)
+            be.call(entry, [L, I, I, I] + [VP] * (11 + nulls), ntok, T, C, 6, P(x), P(mean), P(rstd), P(ln_w), P(ln_b), PA(mus), PA(douts),
+                    P(d3b), *[None] * nulls, P(dx), P(dmu), P(ws))
+            runs.append({"dx": dx, "dmu": dmu})
+        _same_results(runs, f"mix_bwd_ln/{sid}/{'dup3' if d3b is not None else 'plain'}")
+
+    k, v, vf, vl, al = [rnd(be, g, ntok, C) for _ in range(5)]
+    k_k, k_a, a0, v0 = [rnd(be, g, C, scale=0.5) for _ in range(4)]
+    dk2, dv2, dz, db = [rnd(be, g, ntok, C) for _ in range(4)]
+    for vres in (False, True):
+        ins = [P(t) if vres or i not in (1, 2, 3, 8, 10) else None for i, t in enumerate((k, v, vf, vl, al, k_k, k_a, a0, v0, dk2, dv2, dz, db))]
+        runs = []
+        for entry, nulls in (("vrwkv_kva_bwd_bf16", 0), ("vrwkv_kva_bwd2_bf16", 2), ("vrwkv_kva_bwd3_bf16", 3)):
+            bw = {n: nan_rows(be, ntok, C) for n in (("dk", "dv", "dvfirst", "dvl", "dal") if vres else ("dk", "dal"))}
+            pg, ws = nan_rows(be, 4, C, torch.float32), nan_ws(be, ntok, C, 4)
+            be.call(entry, [L, I, I] + [VP] * (20 + nulls), ntok, C, int(vres), *ins, *[None] * nulls,
+                    P(bw["dk"]), P(bw.get("dv")), P(bw.get("dvfirst")), P(bw.get("dvl")), P(bw["dal"]), P(pg), P(ws))
+            runs.append({**bw, "dparams": pg})
+        _same_results(runs, f"kva_bwd/{sid}/{'vres' if vres else 'novres'}")

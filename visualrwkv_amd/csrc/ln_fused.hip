@@ -18,6 +18,7 @@
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
+#include <host_checks.h>
 #include <ln_kernels.h>
 
 namespace {
@@ -53,7 +54,7 @@ inline int ln_threads(int C) { return (C / 8 + 63) / 64 * 64; }
 inline void colsum(int G, long width, const float* part, float* out, hipStream_t st) {
     hipLaunchKernelGGL(ln_colsum_kernel, dim3((unsigned)(width / 16)), dim3(256), 0, st, G, width, part, out);
 }
-inline int done() { hipError_t e = hipGetLastError(); return e == hipSuccess ? VRWKV_OK : (int)e; }
+using hostchk::finish_launch;
 
 // The ln_mix kernels' host side: one description of a launch each way, the variants (the kernels' PK / CARRY / ROUTED flags) its optional
 // fields -- left NULL they select the plain kernel (route: the kernels' own LmRoute).  The vrwkv_ln_mix_* entries below fill one and call
@@ -135,7 +136,7 @@ int ln_mix_fwd(const LnMixFwd& a) {
         pm.p[j] = (const uint16_t*)a.mu[j]; po.p[j] = (uint16_t*)a.out[j];
     }
     if (a.route) ln_mix_fwd_routed(a, pm, po); else ln_mix_fwd_rows(a, pm, po);
-    return done();
+    return finish_launch();
 }
 
 // ws: G (2 + M) C floats, routed G (4 + 2) C -- the (dgamma, dbeta) partial rows of every workgroup, then its dmu rows
@@ -155,7 +156,7 @@ int ln_mix_bwd(const LnMixBwd& a) {
     if (a.route) ln_mix_bwd_routed(a, pm, pd, part); else ln_mix_bwd_rows(a, pm, pd, part);
     colsum(G, w_ln, part.ln, a.dwb, (hipStream_t)a.stream);
     colsum(G, w_mu, part.mu, a.dmu, (hipStream_t)a.stream);
-    return done();
+    return finish_launch();
 }
 
 }  // namespace
@@ -171,7 +172,7 @@ int vrwkv_add_ln_fwd_bf16(long ntok, int C, float eps, const void* x, const void
     hipLaunchKernelGGL(add_ln_fwd_kernel, dim3(ln_grid(ntok)), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, eps,
                        (const uint16_t*)x, (const uint16_t*)delta, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn,
                        (uint16_t*)y, mean, rstd, (const long*)nullptr, (const uint16_t*)nullptr);
-    return done();
+    return finish_launch();
 }
 
 // Inference form for the frozen ViT towers (timm pre-LN blocks, src/vision.py:123-134; SAM blocks, src/sam.py:231-247):
@@ -183,7 +184,7 @@ int vrwkv_add_ln_scaled_fwd_bf16(long ntok, int C, float eps, const void* x, con
     hipLaunchKernelGGL(add_ln_fwd_kernel, dim3(ln_grid(ntok)), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, eps,
                        (const uint16_t*)x, (const uint16_t*)delta, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn,
                        (uint16_t*)y, (float*)nullptr, (float*)nullptr, (const long*)nullptr, (const uint16_t*)dscale);
-    return done();
+    return finish_launch();
 }
 
 // LayerNorm of the projector output written straight into the rows of the token-embedding tensor that hold the image
@@ -198,7 +199,7 @@ int vrwkv_ln_scatter_fwd_bf16(long ntok, int C, float eps, const void* x, const 
     hipLaunchKernelGGL(add_ln_fwd_kernel, dim3(ln_grid(ntok)), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, eps,
                        (const uint16_t*)x, (const uint16_t*)nullptr, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)nullptr,
                        (uint16_t*)out, mean, rstd, row_index, (const uint16_t*)nullptr);
-    return done();
+    return finish_launch();
 }
 
 // ... and its backward: dx[n] = LN'(dout[row_index[n]]), dwb = (dgamma, dbeta); ws as for vrwkv_add_ln_bwd_bf16
@@ -210,7 +211,7 @@ int vrwkv_ln_gather_bwd_bf16(long ntok, int C, const void* dout, const long* row
     hipLaunchKernelGGL(add_ln_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, (const uint16_t*)dout,
                        (const uint16_t*)nullptr, (const uint16_t*)x, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws, row_index);
     colsum(G, 2L * C, ws, dwb, (hipStream_t)stream);
-    return done();
+    return finish_launch();
 }
 
 // The visual token compressor's tail: ln_out, unpad, AdaptiveAvgPool1d over tokens and the scatter into the placeholder rows in one pass
@@ -222,7 +223,7 @@ int vrwkv_ln_pool_scatter_fwd_bf16(int B, int T, int pad, int Lout, int C, float
     hipLaunchKernelGGL(ln_pool_fwd_kernel, dim3(ln_pool_grid((long)B * Lout)), dim3(ln_threads(C)), 0, (hipStream_t)stream, B, T, pad, Lout, C, eps,
                        (const uint16_t*)x, (const uint16_t*)delta, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)xn, (uint16_t*)out, mean, rstd,
                        row_index);
-    return done();
+    return finish_launch();
 }
 
 int vrwkv_ln_pool_gather_bwd_bf16(int B, int T, int pad, int Lout, int C, const void* dout, const long* row_index, const void* xn,
@@ -233,7 +234,7 @@ int vrwkv_ln_pool_gather_bwd_bf16(int B, int T, int pad, int Lout, int C, const 
     hipLaunchKernelGGL(ln_pool_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, B, T, pad, Lout, C, (const uint16_t*)dout, row_index,
                        (const uint16_t*)xn, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws);
     colsum(G, 2L * C, ws, dwb, (hipStream_t)stream);
-    return done();
+    return finish_launch();
 }
 
 // The RWKV vision encoder's tail: ln_out over all rows scattered into the placeholder rows, and the ImageNet head's mean over tokens of the same
@@ -258,7 +259,7 @@ int vrwkv_ln_scatter_mean_fwd_bf16(int B, int L, int C, float eps, const void* x
     const long n = (long)B * C;
     hipLaunchKernelGGL(ln_mean_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, P, C, 1.f / (float)L, ws,
                        (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)pooled);
-    return done();
+    return finish_launch();
 }
 
 // dout (rows of the scattered tensor) and dpooled (B, C) bf16: either may be NULL, not both; row_index NULL: dout is (B L, C) in order.
@@ -272,7 +273,7 @@ int vrwkv_ln_gather_mean_bwd_bf16(int B, int L, int C, const void* dout, const l
     hipLaunchKernelGGL(ln_gather_mean_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, L, C, (const uint16_t*)dout, row_index,
                        (const uint16_t*)dpooled, (const uint16_t*)xn, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws);
     colsum(G, 2L * C, ws, dwb, (hipStream_t)stream);
-    return done();
+    return finish_launch();
 }
 
 int vrwkv_add_ln_bwd_bf16(long ntok, int C, const void* dy, const void* dres, const void* xn, const float* mean,
@@ -283,7 +284,7 @@ int vrwkv_add_ln_bwd_bf16(long ntok, int C, const void* dy, const void* dres, co
     hipLaunchKernelGGL(add_ln_bwd_kernel, dim3(G), dim3(ln_threads(C)), 0, (hipStream_t)stream, ntok, C, (const uint16_t*)dy,
                        (const uint16_t*)dres, (const uint16_t*)xn, mean, rstd, (const uint16_t*)w, (uint16_t*)dx, ws, (const long*)nullptr);
     colsum(G, 2L * C, ws, dwb, (hipStream_t)stream);
-    return done();
+    return finish_launch();
 }
 
 // Residual add + LayerNorm + token shift + M lerps (M = 1: channel-mix, M = 6: time-mix), see ln_mix_fwd_kernel above.
@@ -372,7 +373,7 @@ int vrwkv_row_gather_bf16(long n, int C, const void* src, const void* idx, int i
     const dim3 grid((unsigned)(g > (1L << 20) ? (1L << 20) : g)), block(256);
     if (idx_bytes == 8) hipLaunchKernelGGL(row_gather_kernel<true>, grid, block, 0, (hipStream_t)stream, nvec, C / 8, (const uint16_t*)src, idx, (uint16_t*)dst);
     else hipLaunchKernelGGL(row_gather_kernel<false>, grid, block, 0, (hipStream_t)stream, nvec, C / 8, (const uint16_t*)src, idx, (uint16_t*)dst);
-    return done();
+    return finish_launch();
 }
 
 }  // extern "C"

@@ -12,8 +12,10 @@
 // this is also deterministic).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
+#include <host_checks.h>
 
 namespace {
 
@@ -707,7 +709,90 @@ inline int bwd_grid_pf(long ntok, int C) {
 inline void colsum(int G, long width, const float* part, float* out, hipStream_t st) {
     hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)(width / 16)), dim3(256), 0, st, G, width, part, out);
 }
-inline int done() { hipError_t e = hipGetLastError(); return e == hipSuccess ? VRWKV_OK : (int)e; }
+
+// The host side of every vrwkv_* entry below is: check_rows (the relu^2 pair: check_relusq), for the entries with pointer arrays unpack, the kernel's arguments, one of
+// launch / launch_bwd.  What a defective call is answered, and that it launches nothing, is pinned per entry by tests/test_glue_shapes.py (test_glue_entries_refuse_in_order).
+using hostchk::any_null;
+using hostchk::finish_launch;
+inline const uint16_t* b16(const void* p) { return (const uint16_t*)p; }
+inline uint16_t* b16(void* p) { return (uint16_t*)p; }
+
+// The counts and `bad` -- a NULL among the required pointers, an M or a set of optional pointers that is not built -- are VRWKV_EINVAL and come first; then the row width, and
+// ntok % T of the kernels that shift rows, VRWKV_ESHAPE.
+inline int check_rows(long ntok, int C, bool bad, int T = 1) {
+    if (ntok <= 0 || T <= 0 || bad) return VRWKV_EINVAL;
+    if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
+    return VRWKV_OK;
+}
+inline bool ok_m(int M) { return M == 1 || M == 2 || M == 6; }
+// n elements of an entry's pointer array into a kernel's Ptrs6 / MPtrs6; false: one of them is NULL (VRWKV_EINVAL).  Only the mix and ddmix entries have arrays, and all of
+// them look at the elements AFTER check_rows: a NULL element next to a bad shape is VRWKV_ESHAPE, where a NULL required pointer next to it is VRWKV_EINVAL.
+template <class P6, class V> inline bool unpack(P6& to, V* const* from, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (!from[i]) return false;
+        to.p[i] = static_cast<std::decay_t<decltype(to.p[i])>>(from[i]);
+    }
+    return true;
+}
+
+// One kernel, then the code of the launch.  The forward kernels: tok_grid workgroups of C / 8 threads.
+template <class Kern, class... A> int launch(Kern kern, dim3 grid, int threads, void* stream, A... args) {
+    hipLaunchKernelGGL(kern, grid, dim3(threads), 0, (hipStream_t)stream, args...);
+    return finish_launch();
+}
+// A backward kernel on G workgroups, each of which leaves nvec partial rows of C floats in ws; colsum adds them into dparams.
+template <class Kern, class... A> int launch_bwd(Kern kern, int G, int threads, int nvec, int C, float* ws, float* dparams, void* stream, A... args) {
+    hipLaunchKernelGGL(kern, dim3(G), dim3(threads), 0, (hipStream_t)stream, args...);
+    colsum(G, (long)nvec * C, ws, dparams, (hipStream_t)stream);
+    return finish_launch();
+}
+// kva_bwd / post_bwd: the instantiation whose launch bound covers the C / 8 threads of a row (<256> is the prefetching one), on bwd_grid_pf workgroups.  kern_of(lb) is the
+// caller's kernel template at the launch bound decltype(lb)::value; p its argument block, which begins ntok, C and holds the partial rows as p.part.
+template <class KernOf, class Args> int launch_bwd_by_width(KernOf kern_of, const Args& p, int nvec, float* dparams, void* stream) {
+    auto go = [&](auto lb) { return launch_bwd(kern_of(lb), bwd_grid_pf(p.ntok, p.C), p.C / 8, nvec, p.C, p.part, dparams, stream, p); };
+    if (p.C / 8 <= 256) return go(std::integral_constant<int, 256>{});
+    if (p.C / 8 <= 512) return go(std::integral_constant<int, 512>{});
+    return go(std::integral_constant<int, 1024>{});
+}
+
+// The instantiations of the two lerp kernels.  DD (ddmix: five lerps, per-token weights mm) and LNX (the mix_bwd_ln entries) are template parameters here and not two more
+// run-time choices: kernels enter the code object in the order of their first mention, and so each family is first mentioned where the entry that instantiates its picker
+// stands below -- mix_fwd 6, 2, 1; mix_bwd; mix_bwd with LNX; ddmix forward; ddmix backward -- the order they have had there.
+template <bool DD> int mix_fwd(long ntok, int T, int C, int M, const void* x, const void* x_prev, const Ptrs6& mu, const MPtrs6& out, const Ptrs6& mm, void* stream) {
+    auto go = [&](auto kern) { return launch(kern, tok_grid(ntok, TPB_MIX), C / 8, stream, ntok, T, C, b16(x), b16(x_prev), mu, out, mm); };
+    if constexpr (DD) return go(mix_fwd_kernel<5, true>);
+    else return M == 6 ? go(mix_fwd_kernel<6>) : M == 2 ? go(mix_fwd_kernel<2>) : go(mix_fwd_kernel<1>);
+}
+using MixBwdKern = decltype(&mix_bwd_kernel<1, false>);
+// dup3: dout3_second given (M = 6); pk: `first` given; carry: one of y_prev, dy_last, dy_prev given.  pk with carry is not built: the entries refuse it.
+template <bool DD, bool LNX> MixBwdKern mix_bwd_pick(int M, bool dup3, bool pk, bool carry) {
+    if constexpr (DD) return mix_bwd_kernel<5, false, true>;
+    else if constexpr (LNX) {
+        if (pk) return dup3 ? mix_bwd_kernel<6, true, false, true, true> : mix_bwd_kernel<6, false, false, true, true>;
+        if (!carry) return dup3 ? mix_bwd_kernel<6, true, false, true> : mix_bwd_kernel<6, false, false, true>;
+        return dup3 ? mix_bwd_kernel<6, true, false, true, false, true> : mix_bwd_kernel<6, false, false, true, false, true>;
+    } else {
+        if (M == 6) return dup3 ? mix_bwd_kernel<6, true> : mix_bwd_kernel<6, false>;
+        return M == 2 ? mix_bwd_kernel<2, false> : mix_bwd_kernel<1, false>;
+    }
+}
+// What only some of the mix backward entries have: ddmix mm and dmm, the _ln_ entries ln, _packed first, _carry the last three.
+struct MixBwdOpt {
+    Ptrs6 mm{}; MPtrs6 dmm{}; LnX ln{};
+    const unsigned char* first = nullptr; const void* y_prev = nullptr; const float* dy_last = nullptr; float* dy_prev = nullptr;
+};
+// bwd_grid workgroups with contiguous token ranges, a thread per 4 channels (a channel loop beyond C = 2048), then the M rows of dmu
+int mix_bwd(MixBwdKern kern, long ntok, int T, int C, int M, const void* x, const Ptrs6& mu, const Ptrs6& dout, const void* dout3_second, void* dx, float* dmu, float* ws,
+            void* stream, const MixBwdOpt& o = {}) {
+    return launch_bwd(kern, bwd_grid(ntok), C / 4 < 512 ? C / 4 : 512, M, C, ws, dmu, stream, ntok, T, C, b16(x), mu, dout, b16(dout3_second), b16(dx), ws, o.mm, o.dmm, o.ln,
+                      o.first, b16(o.y_prev), o.dy_last, o.dy_prev);
+}
+
+// relu^2 of n elements: a 16-byte vector per thread, 256 threads per workgroup
+inline int check_relusq(long n, bool bad) {
+    if (n <= 0 || bad) return VRWKV_EINVAL;
+    return n % 8 != 0 || (n / 8 + 255) / 256 > 0x7fffffffL ? VRWKV_ESHAPE : VRWKV_OK;
+}
 
 }  // namespace
 
@@ -719,15 +804,10 @@ int vrwkv_mix_fwd_bf16(long ntok, int T, int C, int M, const void* x, const void
 
 int vrwkv_mix_fwd_prev_bf16(long ntok, int T, int C, int M, const void* x, const void* x_prev, const void* const* mu,
                             void* const* out, void* stream) {
-    if (ntok <= 0 || T <= 0 || !x || !mu || !out || (M != 1 && M != 2 && M != 6)) return VRWKV_EINVAL;
-    if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
+    if (int rc = check_rows(ntok, C, any_null(x, mu, out) || !ok_m(M), T)) return rc;
     Ptrs6 m{}; MPtrs6 o{};
-    for (int i = 0; i < M; ++i) { m.p[i] = (const uint16_t*)mu[i]; o.p[i] = (uint16_t*)out[i]; if (!m.p[i] || !o.p[i]) return VRWKV_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    if (M == 6) hipLaunchKernelGGL(mix_fwd_kernel<6>, tok_grid(ntok, TPB_MIX), dim3(C / 8), 0, st, ntok, T, C, (const uint16_t*)x, (const uint16_t*)x_prev, m, o, Ptrs6{});
-    else if (M == 2) hipLaunchKernelGGL(mix_fwd_kernel<2>, tok_grid(ntok, TPB_MIX), dim3(C / 8), 0, st, ntok, T, C, (const uint16_t*)x, (const uint16_t*)x_prev, m, o, Ptrs6{});
-    else hipLaunchKernelGGL(mix_fwd_kernel<1>, tok_grid(ntok, TPB_MIX), dim3(C / 8), 0, st, ntok, T, C, (const uint16_t*)x, (const uint16_t*)x_prev, m, o, Ptrs6{});
-    return done();
+    if (!unpack(m, mu, M) || !unpack(o, out, M)) return VRWKV_EINVAL;
+    return mix_fwd<false>(ntok, T, C, M, x, x_prev, m, o, Ptrs6{}, stream);
 }
 
 long vrwkv_param_grad_ws_floats(long ntok, int C, int nvec) { return (long)bwd_grid(ntok) * nvec * C; }
@@ -739,50 +819,23 @@ int vrwkv_mix_bwd_bf16(long ntok, int T, int C, int M, const void* x, const void
 
 int vrwkv_mix_bwd2_bf16(long ntok, int T, int C, int M, const void* x, const void* const* mu, const void* const* dout,
                         const void* dout3_second, void* dx, float* dmu, float* ws, void* stream) {
-    if (ntok <= 0 || T <= 0 || !x || !mu || !dout || !dx || !dmu || !ws || (M != 1 && M != 2 && M != 6)) return VRWKV_EINVAL;
-    if (dout3_second && M != 6) return VRWKV_EINVAL;
-    if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
+    if (int rc = check_rows(ntok, C, any_null(x, mu, dout, dx, dmu, ws) || !ok_m(M) || (dout3_second && M != 6), T)) return rc;
     Ptrs6 m{}, d{};
-    for (int i = 0; i < M; ++i) { m.p[i] = (const uint16_t*)mu[i]; d.p[i] = (const uint16_t*)dout[i]; if (!m.p[i] || !d.p[i]) return VRWKV_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    const int G = bwd_grid(ntok);
-    const int threads = C / 4 < 512 ? C / 4 : 512;
-    const uint16_t* d2 = (const uint16_t*)dout3_second;
-    if (M == 6 && d2) hipLaunchKernelGGL((mix_bwd_kernel<6, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)x, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{});
-    else if (M == 6) hipLaunchKernelGGL((mix_bwd_kernel<6, false>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)x, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{});
-    else if (M == 2) hipLaunchKernelGGL((mix_bwd_kernel<2, false>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)x, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{});
-    else hipLaunchKernelGGL((mix_bwd_kernel<1, false>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)x, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{});
-    colsum(G, (long)M * C, ws, dmu, st);
-    return done();
+    if (!unpack(m, mu, M) || !unpack(d, dout, M)) return VRWKV_EINVAL;
+    return mix_bwd(mix_bwd_pick<false, false>(M, dout3_second, false, false), ntok, T, C, M, x, m, d, dout3_second, dx, dmu, ws, stream);
 }
 
 // vrwkv_mix_bwd_ln_bf16 / _packed / _carry: one launch, the variant from the optional pointers -- first: PK; y_prev, dy_last, dy_prev: CARRY; the two
-// together are not built.  (Here and not in the namespace above: kernels enter the code object in the order of their first mention.)
+// together are not built.  (Here, after vrwkv_mix_bwd2_bf16, and not in the namespace above: see mix_bwd_pick.)
 static int mix_bwd_ln(long ntok, int T, int C, int M, const void* xn, const float* mean, const float* rstd, const void* ln_w, const void* ln_b,
                       const void* const* mu, const void* const* dout, const void* dout3_second, const unsigned char* first, const void* y_prev,
                       const float* dy_last, float* dy_prev, void* dx, float* dmu, float* ws, void* stream) {
     const bool carry = y_prev || dy_last || dy_prev;
-    if (ntok <= 0 || T <= 0 || !xn || !mean || !rstd || !ln_w || !ln_b || !mu || !dout || !dx || !dmu || !ws || M != 6 || (first && carry)) return VRWKV_EINVAL;
-    if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
+    if (int rc = check_rows(ntok, C, any_null(xn, mean, rstd, ln_w, ln_b, mu, dout, dx, dmu, ws) || M != 6 || (first && carry), T)) return rc;
     Ptrs6 m{}, d{};
-    for (int i = 0; i < M; ++i) { m.p[i] = (const uint16_t*)mu[i]; d.p[i] = (const uint16_t*)dout[i]; if (!m.p[i] || !d.p[i]) return VRWKV_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    const int G = bwd_grid(ntok);
-    const int threads = C / 4 < 512 ? C / 4 : 512;
-    const uint16_t* d2 = (const uint16_t*)dout3_second;
-    const LnX ln{mean, rstd, (const uint16_t*)ln_w, (const uint16_t*)ln_b};
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)xn, m, d, d2, (uint16_t*)dx, ws, Ptrs6{}, MPtrs6{}, ln, first,
-                           (const uint16_t*)y_prev, dy_last, dy_prev);
-    };
-    if (first && d2) go(mix_bwd_kernel<6, true, false, true, true>);
-    else if (first) go(mix_bwd_kernel<6, false, false, true, true>);
-    else if (!carry && d2) go(mix_bwd_kernel<6, true, false, true>);
-    else if (!carry) go(mix_bwd_kernel<6, false, false, true>);
-    else if (d2) go(mix_bwd_kernel<6, true, false, true, false, true>);
-    else go(mix_bwd_kernel<6, false, false, true, false, true>);
-    colsum(G, (long)M * C, ws, dmu, st);
-    return done();
+    if (!unpack(m, mu, M) || !unpack(d, dout, M)) return VRWKV_EINVAL;
+    const MixBwdOpt o{Ptrs6{}, MPtrs6{}, LnX{mean, rstd, b16(ln_w), b16(ln_b)}, first, y_prev, dy_last, dy_prev};
+    return mix_bwd(mix_bwd_pick<false, true>(M, dout3_second, first, carry), ntok, T, C, M, xn, m, d, dout3_second, dx, dmu, ws, stream, o);
 }
 
 // mix backward when x is the (unstored) LayerNorm output of vrwkv_ln_mix_fwd_bf16: recomputed from xn, mean, rstd, ln_w, ln_b
@@ -810,84 +863,52 @@ int vrwkv_mix_bwd_ln_carry_bf16(long ntok, int T, int C, int M, const void* xn, 
 
 // RWKV-6 data-dependent token shift (VisualRWKV-v6/v6.0/src/model.py:150-160): out_j = x + (x[t-1] - x) (mu_j + mm_j), j < 5.
 int vrwkv_ddmix_fwd_bf16(long ntok, int T, int C, const void* x, const void* const* mu, const void* const* mm, void* const* out, void* stream) {
-    if (ntok <= 0 || T <= 0 || !x || !mu || !mm || !out) return VRWKV_EINVAL;
-    if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
+    if (int rc = check_rows(ntok, C, any_null(x, mu, mm, out), T)) return rc;
     Ptrs6 m{}, t{}; MPtrs6 o{};
-    for (int i = 0; i < 5; ++i) {
-        m.p[i] = (const uint16_t*)mu[i]; t.p[i] = (const uint16_t*)mm[i]; o.p[i] = (uint16_t*)out[i];
-        if (!m.p[i] || !t.p[i] || !o.p[i]) return VRWKV_EINVAL;
-    }
-    hipLaunchKernelGGL((mix_fwd_kernel<5, true>), tok_grid(ntok, TPB_MIX), dim3(C / 8), 0, (hipStream_t)stream, ntok, T, C, (const uint16_t*)x,
-                       (const uint16_t*)nullptr, m, o, t);
-    return done();
+    if (!unpack(m, mu, 5) || !unpack(t, mm, 5) || !unpack(o, out, 5)) return VRWKV_EINVAL;
+    return mix_fwd<true>(ntok, T, C, 5, x, nullptr, m, o, t, stream);
 }
 // backward: dx, dmm_j (ntok, C) bf16 each, dmu = 5*C floats; ws: vrwkv_param_grad_ws_floats(ntok, C, 5)
 int vrwkv_ddmix_bwd_bf16(long ntok, int T, int C, const void* x, const void* const* mu, const void* const* mm, const void* const* dout,
                          void* dx, void* const* dmm, float* dmu, float* ws, void* stream) {
-    if (ntok <= 0 || T <= 0 || !x || !mu || !mm || !dout || !dx || !dmm || !dmu || !ws) return VRWKV_EINVAL;
-    if (!ok_c(C) || ntok % T != 0) return VRWKV_ESHAPE;
-    Ptrs6 m{}, t{}, d{}; MPtrs6 o{};
-    for (int i = 0; i < 5; ++i) {
-        m.p[i] = (const uint16_t*)mu[i]; t.p[i] = (const uint16_t*)mm[i]; d.p[i] = (const uint16_t*)dout[i]; o.p[i] = (uint16_t*)dmm[i];
-        if (!m.p[i] || !t.p[i] || !d.p[i] || !o.p[i]) return VRWKV_EINVAL;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int G = bwd_grid(ntok);
-    const int threads = C / 4 < 512 ? C / 4 : 512;
-    hipLaunchKernelGGL((mix_bwd_kernel<5, false, true>), dim3(G), dim3(threads), 0, st, ntok, T, C, (const uint16_t*)x, m, d, (const uint16_t*)nullptr,
-                       (uint16_t*)dx, ws, t, o);
-    colsum(G, 5L * C, ws, dmu, st);
-    return done();
+    if (int rc = check_rows(ntok, C, any_null(x, mu, mm, dout, dx, dmm, dmu, ws), T)) return rc;
+    Ptrs6 m{}, d{}; MixBwdOpt o;
+    if (!unpack(m, mu, 5) || !unpack(o.mm, mm, 5) || !unpack(d, dout, 5) || !unpack(o.dmm, dmm, 5)) return VRWKV_EINVAL;
+    return mix_bwd(mix_bwd_pick<true, false>(5, false, false, false), ntok, T, C, 5, x, m, d, nullptr, dx, dmu, ws, stream, o);
 }
 
 // RWKV-6 output stage: out = GroupNorm(C/64 groups, eps)(y) * silu(gg)   (model.py:166,176-184)
 int vrwkv_gn_silu_fwd_bf16(long ntok, int C, float eps, const void* y, const void* gg, const void* ln_w, const void* ln_b, void* out, void* stream) {
-    if (ntok <= 0 || !y || !gg || !ln_w || !ln_b || !out) return VRWKV_EINVAL;
-    if (!ok_c(C)) return VRWKV_ESHAPE;
-    hipLaunchKernelGGL(gn_silu_fwd_kernel, tok_grid(ntok, TPB_GN), dim3(C / 8), 0, (hipStream_t)stream, ntok, C, eps, (const uint16_t*)y, (const uint16_t*)gg,
-                       (const uint16_t*)ln_w, (const uint16_t*)ln_b, (uint16_t*)out);
-    return done();
+    if (int rc = check_rows(ntok, C, any_null(y, gg, ln_w, ln_b, out))) return rc;
+    return launch(gn_silu_fwd_kernel, tok_grid(ntok, TPB_GN), C / 8, stream, ntok, C, eps, b16(y), b16(gg), b16(ln_w), b16(ln_b), b16(out));
 }
 // dparams = [dln_w | dln_b] (2 C floats); ws: vrwkv_param_grad_ws_floats(ntok, C, 2)
 int vrwkv_gn_silu_bwd_bf16(long ntok, int C, float eps, const void* y, const void* gg, const void* ln_w, const void* ln_b, const void* dout,
                            void* dy, void* dgg, float* dparams, float* ws, void* stream) {
-    if (ntok <= 0 || !y || !gg || !ln_w || !ln_b || !dout || !dy || !dgg || !dparams || !ws) return VRWKV_EINVAL;
-    if (!ok_c(C)) return VRWKV_ESHAPE;
-    const int G = bwd_grid(ntok);
-    hipLaunchKernelGGL(gn_silu_bwd_kernel, dim3(G), dim3(C / 8), 0, (hipStream_t)stream, ntok, C, eps, (const uint16_t*)y, (const uint16_t*)gg,
-                       (const uint16_t*)ln_w, (const uint16_t*)ln_b, (const uint16_t*)dout, (uint16_t*)dy, (uint16_t*)dgg, ws);
-    colsum(G, 2L * C, ws, dparams, (hipStream_t)stream);
-    return done();
+    if (int rc = check_rows(ntok, C, any_null(y, gg, ln_w, ln_b, dout, dy, dgg, dparams, ws))) return rc;
+    return launch_bwd(gn_silu_bwd_kernel, bwd_grid(ntok), C / 8, 2, C, ws, dparams, stream, ntok, C, eps, b16(y), b16(gg), b16(ln_w), b16(ln_b), b16(dout), b16(dy),
+                      b16(dgg), ws);
 }
 
 int vrwkv_decay_fwd_bf16(long ntok, int C, const void* h, const void* w0, void* w, void* stream) {
-    if (ntok <= 0 || !h || !w0 || !w) return VRWKV_EINVAL;
-    if (!ok_c(C)) return VRWKV_ESHAPE;
-    hipLaunchKernelGGL(decay_fwd_kernel, tok_grid(ntok, TPB_DECAY), dim3(C / 8), 0, (hipStream_t)stream, ntok, C, (const uint16_t*)h, (const uint16_t*)w0, (uint16_t*)w);
-    return done();
+    if (int rc = check_rows(ntok, C, any_null(h, w0, w))) return rc;
+    return launch(decay_fwd_kernel, tok_grid(ntok, TPB_DECAY), C / 8, stream, ntok, C, b16(h), b16(w0), b16(w));
 }
 int vrwkv_decay_bwd_bf16(long ntok, int C, const void* h, const void* w0, const void* dw, void* dh, float* dw0, float* ws, void* stream) {
-    if (ntok <= 0 || !h || !w0 || !dw || !dh || !dw0 || !ws) return VRWKV_EINVAL;
-    if (!ok_c(C)) return VRWKV_ESHAPE;
-    const int G = bwd_grid(ntok);
-    hipLaunchKernelGGL(decay_bwd_kernel, dim3(G), dim3(C / 8), 0, (hipStream_t)stream, ntok, C, (const uint16_t*)h, (const uint16_t*)w0,
-                       (const uint16_t*)dw, (uint16_t*)dh, ws);
-    colsum(G, C, ws, dw0, (hipStream_t)stream);
-    return done();
+    if (int rc = check_rows(ntok, C, any_null(h, w0, dw, dh, dw0, ws))) return rc;
+    return launch_bwd(decay_bwd_kernel, bwd_grid(ntok), C / 8, 1, C, ws, dw0, stream, ntok, C, b16(h), b16(w0), b16(dw), b16(dh), ws);
 }
 
 int vrwkv_kva_fwd_bf16(long ntok, int C, int has_vres, const void* k, const void* v, const void* vfirst, const void* vl, const void* al,
                        const void* k_k, const void* k_a, const void* a0, const void* v0,
                        void* k2, void* v2, void* z, void* b, void* stream) {
-    if (ntok <= 0 || !k || !al || !k_k || !k_a || !a0 || !k2 || !z || !b) return VRWKV_EINVAL;
-    if (has_vres && (!v || !vfirst || !vl || !v0 || !v2)) return VRWKV_EINVAL;
-    if (!ok_c(C)) return VRWKV_ESHAPE;
-    KvaFwd p{ntok, C, has_vres, (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)vfirst, (const uint16_t*)vl, (const uint16_t*)al,
-             (const uint16_t*)k_k, (const uint16_t*)k_a, (const uint16_t*)a0, (const uint16_t*)v0,
-             (uint16_t*)k2, (uint16_t*)v2, (uint16_t*)z, (uint16_t*)b};
-    hipLaunchKernelGGL(kva_fwd_kernel, tok_grid(ntok, TPB_KVA), dim3(C / 8), 0, (hipStream_t)stream, p);
-    return done();
+    if (int rc = check_rows(ntok, C, any_null(k, al, k_k, k_a, a0, k2, z, b) || (has_vres && any_null(v, vfirst, vl, v0, v2)))) return rc;
+    const KvaFwd p{ntok, C, has_vres, b16(k), b16(v), b16(vfirst), b16(vl), b16(al), b16(k_k), b16(k_a), b16(a0), b16(v0), b16(k2), b16(v2), b16(z), b16(b)};
+    return launch(kva_fwd_kernel, tok_grid(ntok, TPB_KVA), C / 8, stream, p);
 }
+// kva backward.  bwd3 is the entry; bwd2 is bwd3 without dvfirst_in, bwd the same without the two *_second.  dk2_second / dv2_second (optional): second gradients of k2 / v2,
+// added to the first.  dvfirst_in (optional): added to dvfirst -- the layers hand the gradient of v_first down a chain instead of each returning its own term for autograd
+// to sum.  dv2_second and dvfirst_in need has_vres.  dparams = [dk_k | dk_a | da0 | dv0], C floats each.
 int vrwkv_kva_bwd_bf16(long ntok, int C, int has_vres, const void* k, const void* v, const void* vfirst, const void* vl, const void* al,
                        const void* k_k, const void* k_a, const void* a0, const void* v0,
                        const void* dk2, const void* dv2, const void* dz, const void* db,
@@ -904,73 +925,41 @@ int vrwkv_kva_bwd2_bf16(long ntok, int C, int has_vres, const void* k, const voi
     return vrwkv_kva_bwd3_bf16(ntok, C, has_vres, k, v, vfirst, vl, al, k_k, k_a, a0, v0, dk2, dv2, dz, db, dk2_second, dv2_second, nullptr,
                                dk, dv, dvfirst, dvl, dal, dparams, ws, stream);
 }
-// dvfirst_in (optional, has_vres only): added to dvfirst -- the layers hand the gradient of v_first down a chain instead of each
-// returning its own term for autograd to sum
 int vrwkv_kva_bwd3_bf16(long ntok, int C, int has_vres, const void* k, const void* v, const void* vfirst, const void* vl, const void* al,
                         const void* k_k, const void* k_a, const void* a0, const void* v0,
                         const void* dk2, const void* dv2, const void* dz, const void* db, const void* dk2_second, const void* dv2_second,
                         const void* dvfirst_in, void* dk, void* dv, void* dvfirst, void* dvl, void* dal,
                         float* dparams, float* ws, void* stream) {
-    if ((dv2_second || dvfirst_in) && !has_vres) return VRWKV_EINVAL;
-    if (ntok <= 0 || !k || !al || !k_k || !k_a || !a0 || !dk2 || !dz || !db || !dk || !dal || !dparams || !ws) return VRWKV_EINVAL;
-    if (has_vres && (!v || !vfirst || !vl || !v0 || !dv2 || !dv || !dvfirst || !dvl)) return VRWKV_EINVAL;
-    if (!ok_c(C)) return VRWKV_ESHAPE;
-    KvaBwd p{ntok, C, has_vres, (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)vfirst, (const uint16_t*)vl, (const uint16_t*)al,
-             (const uint16_t*)k_k, (const uint16_t*)k_a, (const uint16_t*)a0, (const uint16_t*)v0,
-             (const uint16_t*)dk2, (const uint16_t*)dv2, (const uint16_t*)dz, (const uint16_t*)db,
-             (uint16_t*)dk, (uint16_t*)dv, (uint16_t*)dvfirst, (uint16_t*)dvl, (uint16_t*)dal, ws,
-             (const uint16_t*)dk2_second, (const uint16_t*)dv2_second, (const uint16_t*)dvfirst_in};
-    const int G = bwd_grid_pf(ntok, C);
-    if (C / 8 <= 256) hipLaunchKernelGGL(kva_bwd_kernel<256>, dim3(G), dim3(C / 8), 0, (hipStream_t)stream, p);
-    else if (C / 8 <= 512) hipLaunchKernelGGL(kva_bwd_kernel<512>, dim3(G), dim3(C / 8), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(kva_bwd_kernel<1024>, dim3(G), dim3(C / 8), 0, (hipStream_t)stream, p);
-    colsum(G, 4L * C, ws, dparams, (hipStream_t)stream);       // dparams = [dk_k | dk_a | da0 | dv0], C floats each
-    return done();
+    const bool bad = any_null(k, al, k_k, k_a, a0, dk2, dz, db, dk, dal, dparams, ws) || (has_vres && any_null(v, vfirst, vl, v0, dv2, dv, dvfirst, dvl)) ||
+                     ((dv2_second || dvfirst_in) && !has_vres);
+    if (int rc = check_rows(ntok, C, bad)) return rc;
+    const KvaBwd p{ntok, C, has_vres, b16(k), b16(v), b16(vfirst), b16(vl), b16(al), b16(k_k), b16(k_a), b16(a0), b16(v0), b16(dk2), b16(dv2), b16(dz), b16(db),
+                   b16(dk), b16(dv), b16(dvfirst), b16(dvl), b16(dal), ws, b16(dk2_second), b16(dv2_second), b16(dvfirst_in)};
+    return launch_bwd_by_width([](auto lb) { return kva_bwd_kernel<decltype(lb)::value>; }, p, 4, dparams, stream);
 }
 
 int vrwkv_post_fwd_bf16(long ntok, int C, float eps, const void* y, const void* r, const void* k, const void* v, const void* g,
                         const void* ln_w, const void* ln_b, const void* r_k, void* out, void* stream) {
-    if (ntok <= 0 || !y || !r || !k || !v || !g || !ln_w || !ln_b || !r_k || !out) return VRWKV_EINVAL;
-    if (!ok_c(C)) return VRWKV_ESHAPE;
-    PostFwd p{ntok, C, eps, (const uint16_t*)y, (const uint16_t*)r, (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)g,
-              (const uint16_t*)ln_w, (const uint16_t*)ln_b, (const uint16_t*)r_k, (uint16_t*)out};
-    hipLaunchKernelGGL(post_fwd_kernel, tok_grid(ntok, TPB_POST), dim3(C / 8), 0, (hipStream_t)stream, p);
-    return done();
+    if (int rc = check_rows(ntok, C, any_null(y, r, k, v, g, ln_w, ln_b, r_k, out))) return rc;
+    const PostFwd p{ntok, C, eps, b16(y), b16(r), b16(k), b16(v), b16(g), b16(ln_w), b16(ln_b), b16(r_k), b16(out)};
+    return launch(post_fwd_kernel, tok_grid(ntok, TPB_POST), C / 8, stream, p);
 }
+// dparams = [dln_w | dln_b | dr_k]
 int vrwkv_post_bwd_bf16(long ntok, int C, float eps, const void* y, const void* r, const void* k, const void* v, const void* g,
                         const void* ln_w, const void* ln_b, const void* r_k, const void* dout,
                         void* dy, void* dr, void* dk, void* dv, void* dg, float* dparams, float* ws, void* stream) {
-    if (ntok <= 0 || !y || !r || !k || !v || !g || !ln_w || !ln_b || !r_k || !dout || !dy || !dr || !dk || !dv || !dg || !dparams || !ws)
-        return VRWKV_EINVAL;
-    if (!ok_c(C)) return VRWKV_ESHAPE;
-    PostBwd p{ntok, C, eps, (const uint16_t*)y, (const uint16_t*)r, (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)g,
-              (const uint16_t*)ln_w, (const uint16_t*)ln_b, (const uint16_t*)r_k, (const uint16_t*)dout,
-              (uint16_t*)dy, (uint16_t*)dr, (uint16_t*)dk, (uint16_t*)dv, (uint16_t*)dg, ws};
-    const int G = bwd_grid_pf(ntok, C);
-    if (C / 8 <= 256) hipLaunchKernelGGL(post_bwd_kernel<256>, dim3(G), dim3(C / 8), 0, (hipStream_t)stream, p);
-    else if (C / 8 <= 512) hipLaunchKernelGGL(post_bwd_kernel<512>, dim3(G), dim3(C / 8), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(post_bwd_kernel<1024>, dim3(G), dim3(C / 8), 0, (hipStream_t)stream, p);
-    colsum(G, 3L * C, ws, dparams, (hipStream_t)stream);       // dparams = [dln_w | dln_b | dr_k]
-    return done();
+    if (int rc = check_rows(ntok, C, any_null(y, r, k, v, g, ln_w, ln_b, r_k, dout, dy, dr, dk, dv, dg, dparams, ws))) return rc;
+    const PostBwd p{ntok, C, eps, b16(y), b16(r), b16(k), b16(v), b16(g), b16(ln_w), b16(ln_b), b16(r_k), b16(dout), b16(dy), b16(dr), b16(dk), b16(dv), b16(dg), ws};
+    return launch_bwd_by_width([](auto lb) { return post_bwd_kernel<decltype(lb)::value>; }, p, 3, dparams, stream);
 }
 
 int vrwkv_relusq_fwd_bf16(long n, const void* h, void* y, void* stream) {
-    if (n <= 0 || !h || !y) return VRWKV_EINVAL;
-    if (n % 8 != 0) return VRWKV_ESHAPE;
-    const long n8 = n / 8;
-    const long blocks = (n8 + 255) / 256;
-    if (blocks > 0x7fffffffL) return VRWKV_ESHAPE;
-    hipLaunchKernelGGL(relusq_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n8, (const uint16_t*)h, (uint16_t*)y);
-    return done();
+    if (int rc = check_relusq(n, any_null(h, y))) return rc;
+    return launch(relusq_fwd_kernel, dim3((unsigned)((n / 8 + 255) / 256)), 256, stream, n / 8, b16(h), b16(y));
 }
 int vrwkv_relusq_bwd_bf16(long n, const void* h, const void* dy, void* dh, void* stream) {
-    if (n <= 0 || !h || !dy || !dh) return VRWKV_EINVAL;
-    if (n % 8 != 0) return VRWKV_ESHAPE;
-    const long n8 = n / 8;
-    const long blocks = (n8 + 255) / 256;
-    if (blocks > 0x7fffffffL) return VRWKV_ESHAPE;
-    hipLaunchKernelGGL(relusq_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n8, (const uint16_t*)h, (const uint16_t*)dy, (uint16_t*)dh);
-    return done();
+    if (int rc = check_relusq(n, any_null(h, dy, dh))) return rc;
+    return launch(relusq_bwd_kernel, dim3((unsigned)((n / 8 + 255) / 256)), 256, stream, n / 8, b16(h), b16(dy), b16(dh));
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <atomic>
 
 #include "../../include/visualrwkv_hip.h"
+#include <host_checks.h>
 #include <wkv7_kernels.h>
 
 namespace wkv7launch {
@@ -17,16 +18,13 @@ constexpr long FWD_ISPLIT_MAX_HEADS = 128;
 constexpr int BWD_V5_MODE = 2 + 4 + 128;
 
 inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }      // NULL is not misaligned
-template <class... Ptr> inline bool any_null(Ptr... p) { return (... || (p == nullptr)); }
+using hostchk::any_null;
+using hostchk::finish_launch;
 template <class... Ptr> inline bool any_misaligned(Ptr... p) { return (... || misaligned(p)); }
 inline int check_common(int B, int T, int H) {
     if (B <= 0 || T <= 0 || H <= 0) return VRWKV_EINVAL;
     if (T % VRWKV_CHUNK_LEN != 0) return VRWKV_ESHAPE;   // cuda_backward asserts this, wkv7_cuda.cu:136
     return VRWKV_OK;
-}
-inline int finish_launch() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
 }
 // dynamic-LDS launch of a kernel taking one argument block
 template <class Args>

@@ -43,6 +43,25 @@ def _ws(ntok, C, nvec, device):
     return torch.empty(n, dtype=torch.float32, device=device)
 
 
+def _glue(name, *args, like):
+    """One launch of the library entry `name` on PyTorch's current stream of like's device.  The entry gets `args` -- tensors as pointers, None
+    as NULL, lists of tensors as pointer arrays, numbers as they are -- then the stream; a code other than 0 raises (hip_lib.check)."""
+    Tensor = torch.Tensor                     # the common case first: this runs once per launch, 26 arguments for kva's backward
+    conv = [a.data_ptr() if isinstance(a, Tensor) else 0 if a is None else _ptr_array(a) if isinstance(a, (list, tuple)) else a for a in args]
+    hip_lib.check(getattr(hip_lib.load(), name)(*conv, _stream(like)), name)
+
+
+def _grad_rows(ntok, C, nvec, device):
+    """What a glue backward entry writes its parameter gradients through: (the nvec fp32 rows of C, the workspace of its partial rows)."""
+    return torch.empty(nvec, C, dtype=torch.float32, device=device), _ws(ntok, C, nvec, device)
+
+
+def _rows_as(pg, dtype, shapes):
+    """The fp32 gradient rows in the parameters' dtype, row i in the shape shapes[i] (None: there is no such parameter)."""
+    pg = pg.to(dtype)
+    return [pg[i].view(s) if s is not None else None for i, s in enumerate(shapes)]
+
+
 def wgrad_skinny_supported(x2d, dy2d):
     K, N = x2d.shape[1], dy2d.shape[1]
     nw, d = max(K, N), min(K, N)
@@ -297,8 +316,7 @@ class _Mix(torch.autograd.Function):
         mus_c = [m.reshape(C).contiguous() for m in mus]
         _chk(x, *mus_c)
         outs = [torch.empty_like(x) for _ in mus]
-        rc = hip_lib.load().vrwkv_mix_fwd_bf16(B * T, T, C, len(mus), x.data_ptr(), _ptr_array(mus_c), _ptr_array(outs), _stream(x))
-        hip_lib.check(rc, "vrwkv_mix_fwd_bf16")
+        _glue("vrwkv_mix_fwd_bf16", B * T, T, C, len(mus), x, mus_c, outs, like=x)
         ctx.save_for_backward(x, *mus_c)
         ctx.mu_shapes = [m.shape for m in mus]
         if dup3:                 # a 7th output aliasing output 3 (x_v) for its second consumer
@@ -314,13 +332,9 @@ class _Mix(torch.autograd.Function):
         M = len(mus_c)
         second = douts[M] if len(douts) > M else None          # gradient of the alias of output 3
         dx = torch.empty_like(x)
-        dmu = torch.empty(M, C, dtype=torch.float32, device=x.device)
-        ws = _ws(B * T, C, M, x.device)
-        rc = hip_lib.load().vrwkv_mix_bwd2_bf16(B * T, T, C, M, x.data_ptr(), _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second),
-                                                dx.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(x))
-        hip_lib.check(rc, "vrwkv_mix_bwd2_bf16")
-        dmu = dmu.to(x.dtype)
-        return (dx, *[dmu[i].view(s) for i, s in enumerate(ctx.mu_shapes)])
+        dmu, ws = _grad_rows(B * T, C, M, x.device)
+        _glue("vrwkv_mix_bwd2_bf16", B * T, T, C, M, x, mus_c, douts[:M], second, dx, dmu, ws, like=x)
+        return (dx, *_rows_as(dmu, x.dtype, ctx.mu_shapes))
 
 
 class _MixDup3(_Mix):
@@ -342,8 +356,7 @@ class _Decay(torch.autograd.Function):
         w0c = w0.reshape(C).contiguous()
         _chk(h, w0c)
         w = torch.empty_like(h)
-        rc = hip_lib.load().vrwkv_decay_fwd_bf16(h.numel() // C, C, h.data_ptr(), w0c.data_ptr(), w.data_ptr(), _stream(h))
-        hip_lib.check(rc, "vrwkv_decay_fwd_bf16")
+        _glue("vrwkv_decay_fwd_bf16", h.numel() // C, C, h, w0c, w, like=h)
         ctx.save_for_backward(h, w0c)
         ctx.w0_shape = w0.shape
         return w
@@ -355,12 +368,9 @@ class _Decay(torch.autograd.Function):
         dw = dw.contiguous()
         _chk(dw)
         dh = torch.empty_like(h)
-        dw0 = torch.empty(C, dtype=torch.float32, device=h.device)
-        ws = _ws(h.numel() // C, C, 1, h.device)
-        rc = hip_lib.load().vrwkv_decay_bwd_bf16(h.numel() // C, C, h.data_ptr(), w0c.data_ptr(), dw.data_ptr(), dh.data_ptr(),
-                                                 dw0.data_ptr(), ws.data_ptr(), _stream(h))
-        hip_lib.check(rc, "vrwkv_decay_bwd_bf16")
-        return dh, dw0.to(h.dtype).view(ctx.w0_shape)
+        dw0, ws = _grad_rows(h.numel() // C, C, 1, h.device)
+        _glue("vrwkv_decay_bwd_bf16", h.numel() // C, C, h, w0c, dw, dh, dw0, ws, like=h)
+        return dh, *_rows_as(dw0, h.dtype, [ctx.w0_shape])
 
 
 class _Kva(torch.autograd.Function):
@@ -387,10 +397,7 @@ class _Kva(torch.autograd.Function):
         _chk(k, al, v, v_first, vl, pk, pa, p0, pv)
         k2, z, b = torch.empty_like(k), torch.empty_like(k), torch.empty_like(k)
         v2 = torch.empty_like(k) if has else None
-        rc = hip_lib.load().vrwkv_kva_fwd_bf16(ntok, C, int(has), k.data_ptr(), _p(v), _p(v_first), _p(vl), al.data_ptr(),
-                                               pk.data_ptr(), pa.data_ptr(), p0.data_ptr(), _p(pv),
-                                               k2.data_ptr(), _p(v2), z.data_ptr(), b.data_ptr(), _stream(k))
-        hip_lib.check(rc, "vrwkv_kva_fwd_bf16")
+        _glue("vrwkv_kva_fwd_bf16", ntok, C, int(has), k, v, v_first, vl, al, pk, pa, p0, pv, k2, v2, z, b, like=k)
         ctx.has = has
         ctx.dup = bool(dup)
         ctx.chain = chain
@@ -426,21 +433,11 @@ class _Kva(torch.autograd.Function):
         C = k.shape[-1]
         ntok = k.numel() // C
         dk, dal = torch.empty_like(k), torch.empty_like(k)
-        dv = torch.empty_like(k) if has else None
-        dvf = torch.empty_like(k) if has else None
-        dvl = torch.empty_like(k) if has else None
-        pg = torch.empty(4, C, dtype=torch.float32, device=k.device)
-        ws = _ws(ntok, C, 4, k.device)
-        rc = hip_lib.load().vrwkv_kva_bwd3_bf16(ntok, C, int(has), k.data_ptr(), _p(v), _p(v_first), _p(vl), al.data_ptr(),
-                                                pk.data_ptr(), pa.data_ptr(), p0.data_ptr(), _p(pv),
-                                                dk2.data_ptr(), _p(dv2), dz.data_ptr(), db.data_ptr(), _p(dk2b), _p(dv2b), _p(dvf_in),
-                                                dk.data_ptr(), _p(dv), _p(dvf), _p(dvl), dal.data_ptr(),
-                                                pg.data_ptr(), ws.data_ptr(), _stream(k))
-        hip_lib.check(rc, "vrwkv_kva_bwd3_bf16")
-        pgb = pg.to(k.dtype)
-        s = ctx.shapes
-        res = (dk, dv, dvf, dvl, dal, pgb[0].view(s[0]), pgb[1].view(s[1]), pgb[2].view(s[2]), pgb[3].view(s[3]) if has else None)
-        return res + (None,) * ctx.nflags          # dup, chain
+        dv, dvf, dvl = [torch.empty_like(k) if has else None for _ in range(3)]
+        pg, ws = _grad_rows(ntok, C, 4, k.device)
+        _glue("vrwkv_kva_bwd3_bf16", ntok, C, int(has), k, v, v_first, vl, al, pk, pa, p0, pv, dk2, dv2, dz, db, dk2b, dv2b, dvf_in,
+              dk, dv, dvf, dvl, dal, pg, ws, like=k)
+        return (dk, dv, dvf, dvl, dal, *_rows_as(pg, k.dtype, ctx.shapes)) + (None,) * ctx.nflags          # dup, chain
 
 
 class _Post(torch.autograd.Function):
@@ -453,9 +450,7 @@ class _Post(torch.autograd.Function):
         lw, lb, rk = ln_w.contiguous(), ln_b.contiguous(), r_k.reshape(C).contiguous()
         _chk(y, r, k, v, g, lw, lb, rk)
         out = torch.empty_like(y)
-        rc = hip_lib.load().vrwkv_post_fwd_bf16(y.numel() // C, C, float(eps), y.data_ptr(), r.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                                g.data_ptr(), lw.data_ptr(), lb.data_ptr(), rk.data_ptr(), out.data_ptr(), _stream(y))
-        hip_lib.check(rc, "vrwkv_post_fwd_bf16")
+        _glue("vrwkv_post_fwd_bf16", y.numel() // C, C, float(eps), y, r, k, v, g, lw, lb, rk, out, like=y)
         ctx.save_for_backward(y, r, k, v, g, lw, lb, rk)
         ctx.eps = float(eps)
         ctx.rk_shape = r_k.shape
@@ -468,15 +463,21 @@ class _Post(torch.autograd.Function):
         _chk(dout)
         C = y.shape[-1]
         dy, dr, dk, dv, dg = [torch.empty_like(y) for _ in range(5)]
-        pg = torch.empty(3, C, dtype=torch.float32, device=y.device)
-        ws = _ws(y.numel() // C, C, 3, y.device)
-        rc = hip_lib.load().vrwkv_post_bwd_bf16(y.numel() // C, C, ctx.eps, y.data_ptr(), r.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                                g.data_ptr(), lw.data_ptr(), lb.data_ptr(), rk.data_ptr(), dout.data_ptr(),
-                                                dy.data_ptr(), dr.data_ptr(), dk.data_ptr(), dv.data_ptr(), dg.data_ptr(),
-                                                pg.data_ptr(), ws.data_ptr(), _stream(y))
-        hip_lib.check(rc, "vrwkv_post_bwd_bf16")
-        pgb = pg.to(y.dtype)
-        return dy, dr, dk, dv, dg, pgb[0], pgb[1], pgb[2].view(ctx.rk_shape), None
+        pg, ws = _grad_rows(y.numel() // C, C, 3, y.device)
+        _glue("vrwkv_post_bwd_bf16", y.numel() // C, C, ctx.eps, y, r, k, v, g, lw, lb, rk, dout, dy, dr, dk, dv, dg, pg, ws, like=y)
+        return dy, dr, dk, dv, dg, *_rows_as(pg, y.dtype, [(C,), (C,), ctx.rk_shape]), None
+
+
+def _relusq_fwd(h):
+    y = torch.empty_like(h)
+    _glue("vrwkv_relusq_fwd_bf16", h.numel(), h, y, like=h)
+    return y
+
+
+def _relusq_bwd(h, dy):
+    dh = torch.empty_like(h)
+    _glue("vrwkv_relusq_bwd_bf16", h.numel(), h, dy, dh, like=h)
+    return dh
 
 
 class _ReluSq(torch.autograd.Function):
@@ -484,21 +485,15 @@ class _ReluSq(torch.autograd.Function):
     def forward(ctx, h):
         h = h.contiguous()
         _chk(h)
-        y = torch.empty_like(h)
-        rc = hip_lib.load().vrwkv_relusq_fwd_bf16(h.numel(), h.data_ptr(), y.data_ptr(), _stream(h))
-        hip_lib.check(rc, "vrwkv_relusq_fwd_bf16")
         ctx.save_for_backward(h)
-        return y
+        return _relusq_fwd(h)
 
     @staticmethod
     def backward(ctx, dy):
         (h,) = ctx.saved_tensors
         dy = dy.contiguous()
         _chk(dy)
-        dh = torch.empty_like(h)
-        rc = hip_lib.load().vrwkv_relusq_bwd_bf16(h.numel(), h.data_ptr(), dy.data_ptr(), dh.data_ptr(), _stream(h))
-        hip_lib.check(rc, "vrwkv_relusq_bwd_bf16")
-        return dh
+        return _relusq_bwd(h, dy)
 
 
 class _ReluSqLinear(torch.autograd.Function):
@@ -510,16 +505,13 @@ class _ReluSqLinear(torch.autograd.Function):
     def forward(ctx, h, w):
         h = h.contiguous()
         _chk(h)
-        y = torch.empty_like(h)
-        hip_lib.check(hip_lib.load().vrwkv_relusq_fwd_bf16(h.numel(), h.data_ptr(), y.data_ptr(), _stream(h)), "vrwkv_relusq_fwd_bf16")
         ctx.save_for_backward(h, w)
         ctx.wparam = w if hasattr(w, "_vrwkv_flat_grad") else None
-        return F.linear(y, w)
+        return F.linear(_relusq_fwd(h), w)
 
     @staticmethod
     def backward(ctx, dy):
         h, w = ctx.saved_tensors
-        lib = hip_lib.load()
         dy = dy.contiguous()
         dw = None
         both = (ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
@@ -530,15 +522,13 @@ class _ReluSqLinear(torch.autograd.Function):
             if both:
                 side.wait_stream(cur)
             with torch.cuda.stream(side):
-                y = torch.empty_like(h)
-                hip_lib.check(lib.vrwkv_relusq_fwd_bf16(h.numel(), h.data_ptr(), y.data_ptr(), _stream(h)), "vrwkv_relusq_fwd_bf16")
+                y = _relusq_fwd(h)
                 dw = _weight_grad(ctx.wparam, dy.reshape(-1, dy.shape[-1]), y.reshape(-1, y.shape[-1]))
                 del y
         dh = None
         if ctx.needs_input_grad[0]:
             dyy = F.linear(dy, transpose2d(w))               # gradient of relu(h)^2 (the allocator hands it the bytes just freed)
-            dh = torch.empty_like(h)
-            hip_lib.check(lib.vrwkv_relusq_bwd_bf16(h.numel(), h.data_ptr(), dyy.data_ptr(), dh.data_ptr(), _stream(h)), "vrwkv_relusq_bwd_bf16")
+            dh = _relusq_bwd(h, dyy)
         if both:
             cur.wait_stream(side)
             dw.record_stream(cur)
@@ -587,8 +577,7 @@ def _add_ln_bwd(dy, d_xn, xn, mean, rstd, wc):
 
 def _param_grads(dwb, dmu, wc, xn, mu_shapes):
     """The fp32 parameter gradients in the parameters' dtypes and shapes: (dwb, [dmu_j])."""
-    dmu = dmu.to(xn.dtype)
-    return dwb.to(wc.dtype), [dmu[i].view(sh) for i, sh in enumerate(mu_shapes)]
+    return dwb.to(wc.dtype), _rows_as(dmu, xn.dtype, mu_shapes)
 
 
 class _AddLN(torch.autograd.Function):
@@ -1268,9 +1257,7 @@ class _DDMix(torch.autograd.Function):
         _chk(x, mm, *mus_c)
         assert len(mus) == 5 and tuple(mm.shape) == (5, B, T, C)
         outs = [torch.empty_like(x) for _ in range(5)]
-        rc = hip_lib.load().vrwkv_ddmix_fwd_bf16(B * T, T, C, x.data_ptr(), _ptr_array(mus_c), _ptr_array(list(mm.unbind(0))),
-                                                 _ptr_array(outs), _stream(x))
-        hip_lib.check(rc, "vrwkv_ddmix_fwd_bf16")
+        _glue("vrwkv_ddmix_fwd_bf16", B * T, T, C, x, mus_c, mm.unbind(0), outs, like=x)
         ctx.save_for_backward(x, mm, *mus_c)
         ctx.mu_shapes = [m.shape for m in mus]
         return tuple(outs)
@@ -1281,16 +1268,10 @@ class _DDMix(torch.autograd.Function):
         B, T, C = x.shape
         douts = [d.contiguous() for d in douts]
         _chk(*douts)
-        dx = torch.empty_like(x)
-        dmm = torch.empty_like(mm)
-        dmu = torch.empty(5, C, dtype=torch.float32, device=x.device)
-        ws = _ws(B * T, C, 5, x.device)
-        rc = hip_lib.load().vrwkv_ddmix_bwd_bf16(B * T, T, C, x.data_ptr(), _ptr_array(mus_c), _ptr_array(list(mm.unbind(0))),
-                                                 _ptr_array(douts), dx.data_ptr(), _ptr_array(list(dmm.unbind(0))), dmu.data_ptr(),
-                                                 ws.data_ptr(), _stream(x))
-        hip_lib.check(rc, "vrwkv_ddmix_bwd_bf16")
-        dmu = dmu.to(x.dtype)
-        return (dx, dmm, *[dmu[i].view(s) for i, s in enumerate(ctx.mu_shapes)])
+        dx, dmm = torch.empty_like(x), torch.empty_like(mm)
+        dmu, ws = _grad_rows(B * T, C, 5, x.device)
+        _glue("vrwkv_ddmix_bwd_bf16", B * T, T, C, x, mus_c, mm.unbind(0), douts, dx, dmm.unbind(0), dmu, ws, like=x)
+        return (dx, dmm, *_rows_as(dmu, x.dtype, ctx.mu_shapes))
 
 
 class _GnSilu(torch.autograd.Function):
@@ -1303,9 +1284,7 @@ class _GnSilu(torch.autograd.Function):
         lw, lb = ln_w.contiguous(), ln_b.contiguous()
         _chk(y, gg, lw, lb)
         out = torch.empty_like(y)
-        rc = hip_lib.load().vrwkv_gn_silu_fwd_bf16(y.numel() // C, C, float(eps), y.data_ptr(), gg.data_ptr(), lw.data_ptr(), lb.data_ptr(),
-                                                   out.data_ptr(), _stream(y))
-        hip_lib.check(rc, "vrwkv_gn_silu_fwd_bf16")
+        _glue("vrwkv_gn_silu_fwd_bf16", y.numel() // C, C, float(eps), y, gg, lw, lb, out, like=y)
         ctx.save_for_backward(y, gg, lw, lb)
         ctx.eps = float(eps)
         return out
@@ -1317,13 +1296,9 @@ class _GnSilu(torch.autograd.Function):
         _chk(dout)
         C = y.shape[-1]
         dy, dgg = torch.empty_like(y), torch.empty_like(gg)
-        pg = torch.empty(2, C, dtype=torch.float32, device=y.device)
-        ws = _ws(y.numel() // C, C, 2, y.device)
-        rc = hip_lib.load().vrwkv_gn_silu_bwd_bf16(y.numel() // C, C, ctx.eps, y.data_ptr(), gg.data_ptr(), lw.data_ptr(), lb.data_ptr(),
-                                                   dout.data_ptr(), dy.data_ptr(), dgg.data_ptr(), pg.data_ptr(), ws.data_ptr(), _stream(y))
-        hip_lib.check(rc, "vrwkv_gn_silu_bwd_bf16")
-        pgb = pg.to(y.dtype)
-        return dy, dgg, pgb[0], pgb[1], None
+        pg, ws = _grad_rows(y.numel() // C, C, 2, y.device)
+        _glue("vrwkv_gn_silu_bwd_bf16", y.numel() // C, C, ctx.eps, y, gg, lw, lb, dout, dy, dgg, pg, ws, like=y)
+        return dy, dgg, *_rows_as(pg, y.dtype, [(C,), (C,)]), None
 
 
 ddmix = _DDMix.apply
