@@ -280,6 +280,12 @@ int vrwkv_gemv_multi_bf16(int n_jobs, int B, const void* const* W, const void* c
 int vrwkv_gemv_multi_copy_bf16(int n_jobs, int B, const void* const* W, const void* const* x, const void* const* res,
                                void* const* y, const int* N, const int* K, const int* act, const void* copy_src,
                                void* copy_dst, long copy_elems, void* stream);
+/* Same with a gate: y_j = res_j + gate_j * act_j(W_j x_j), gate_j (B,N_j) bf16, never NULL (VRWKV_EINVAL); fp32 up to the one rounding of
+ * y.  The channel mix of RWKV-6 at T = 1, x + sigmoid(receptance(xr)) * value(k) (VisualRWKV-v6/v6.0/src/model.py:198-226), with the carried
+ * row's replacement as the side job.  With gate = 1 the result is vrwkv_gemv_multi_copy_bf16's bit for bit. */
+int vrwkv_gemv_gated_copy_bf16(int n_jobs, int B, const void* const* W, const void* const* x, const void* const* res,
+                               const void* const* gate, void* const* y, const int* N, const int* K, const int* act,
+                               const void* copy_src, void* copy_dst, long copy_elems, void* stream);
 /* Batched GEMV with LayerNorm + token shift + lerp folded into the input (Block.forward's ln1 / ln2 followed by the
  * lerps of src/model.py:169-173,222-223 at T = 1):  h = LayerNorm(x; ln_w, ln_b, eps),  in_j = h + (x_prev - h) mu_j,
  * y_j = act_j(W_j in_j).  All jobs share x (B,K) and K (512 <= K <= 4096); h is also written to h_out (B,K).  x_prev is
@@ -311,6 +317,30 @@ int vrwkv_decode_tmix_head_bf16(int B, int H, const void* r, const void* k, cons
  * i = value row, j = key column, updated in place.  (The training op's checkpoint `s` holds S^T.) */
 int vrwkv_wkv7_step_bf16(int B, int H, const void* w, const void* q, const void* k, const void* v,
                          const void* z, const void* a, float* state, void* y, void* stream);
+
+/* RWKV-6 decode step (stateful generation; the reference re-runs the whole text pass per new token).  B <= 4, head size 64,
+ * C = 64 H, C % 64 == 0, C <= 8192 (VRWKV_ESHAPE otherwise); B outside 1..4 or a NULL pointer: VRWKV_EINVAL; every pointer 16-byte
+ * aligned (VRWKV_EALIGN).  A refused call writes nothing.
+ *
+ * WKV6 single-token step (kernel_forward of cuda/wkv6_cuda.cu at T = 1; the time-mix of VisualRWKV-v6/v6.0/src/model.py:92-226 with the
+ * carried state of v6.xx/src/model.py:137-144).  r, k, v, w_raw, y: (B,H,64) bf16; u: (H,64) bf16 (time_faaaa); state: (B,H,64,64) f32
+ * [key i][value j] -- the layout of vrwkv_wkv6_forward_state_bf16 -- updated in place:
+ *   y[j] = sum_i r[i] (u[i] k[i] v[j] + S[i][j]),  then  S[i][j] = S[i][j] exp(-exp(w_raw[i])) + k[i] v[j]. */
+int vrwkv_wkv6_step_bf16(int B, int H, const void* r, const void* k, const void* v, const void* w_raw, const void* u,
+                         float* state, void* y, void* stream);
+/* Second stage of the five-way data-dependent token shift (RWKV_Tmix_x060.mix, v6.0/src/model.py:92-226): h (B,C) = the ln1 row,
+ * x_prev (B,C) = the carried row, hid (B,5 D) = tanh(xxx time_maa_w1), w2 = time_maa_w2 (5,D,C) as stored, maa[5] = time_maa_{w,k,v,r,g}
+ * (C) in the order of w2's first dimension.  out[j] (B,C) = h + (x_prev - h) (maa_j + hid_j w2_j[:, c]), rounded once; then x_prev = h.
+ * D in {32, 64}. */
+int vrwkv_decode6_ddlerp_bf16(int B, int C, int D, const void* h, void* x_prev, const void* hid, const void* w2,
+                              const void* const* maa, void* const* out, void* stream);
+/* One workgroup per (b, head): w_raw = bf16(bf16(hid time_decay_w2) + time_decay) with hid (B,d_decay) = tanh(xw time_decay_w1) and
+ * w2 = time_decay_w2 (d_decay,C) as stored, d_decay in {64, 128}; the step above on `state` in place with u = time_faaaa; y rounded to
+ * bf16; GroupNorm ln_x over the head (eps = 1e-5 head_size_divisor^2); times silu(g), g (B,C) the raw gate product
+ * (v6.0/src/model.py:92-226 between the projections and the output projection; v6.xx/src/model.py:137-144).  r, k, v, g, out: (B,C). */
+int vrwkv_decode6_tmix_head_bf16(int B, int H, int d_decay, const void* r, const void* k, const void* v, const void* g,
+                                 const void* hid, const void* w2, const void* time_decay, const void* u, const void* ln_w,
+                                 const void* ln_b, float eps, float* state, void* out, void* stream);
 
 /* Kernel-generation override for tests and A/B benchmarks; -1 restores the default.
  * forward:  -1 = the default: csrc/wkv7_fwd_v4.h (chunked MFMA kernel with producer / consumer waves; rows in by LDS-DMA, results out

@@ -13,6 +13,10 @@
 //   256 workgroups, and the whole matrix is in flight at once -- the step is bound by one HBM round trip per launch.
 //   short rows (K < 512): a group of G = K/8 lanes per row, 64/G rows at a time, x staged in LDS as fp32.
 //
+// Gated entry (vrwkv_gemv_gated_copy_bf16): y_j = res_j + gate_j * act_j(W_j x_j), the RWKV-6 channel mix's
+// x + sigmoid(W_r x_r) (W_v k) (VisualRWKV-v6/v6.0/src/model.py:198-226) in the epilogue of the value GEMV; its own instantiation
+// of the kernel, the other entries launch the one without the gate.
+//
 // LayerNorm fold (vrwkv_gemv_ln_multi_bf16, long rows, K <= 4096): the jobs share one raw residual row x; every
 // workgroup rebuilds its job's input  in_j = h + (x_prev - h) mu_j,  h = LayerNorm(x)  (Block.forward's ln1 / ln2 + the
 // token-shift lerps of src/model.py:169-173,222-223,250,253) from a few KB that sit in L2 -- cheaper than the ~7 us a
@@ -44,6 +48,7 @@ struct GemvJob {
     const uint16_t* x;
     const uint16_t* res;      // optional (B,N): added after the activation
     const uint16_t* mu;       // LayerNorm fold: this job's lerp coefficients (K)
+    const uint16_t* gate;     // gated entry: (B,N), multiplies the activated product before the residual
     uint16_t* y;
     int N, K, act;            // act: 0 none, 1 tanh, 2 sigmoid, 3 relu^2
     int wg_begin;             // first workgroup of this job
@@ -67,6 +72,15 @@ DEVFN float apply_act(float v, int act) {
     if (act == 2) return 1.f / (1.f + fast_exp(-v));
     if (act == 3) { const float r = fmaxf(v, 0.f); return r * r; }
     return v;
+}
+
+// y[b][n] = act(v) (* gate) (+ res), rounded once: the epilogue of all three K paths.  GATED is compiled in for the gated entry alone.
+template <bool GATED>
+DEVFN void emit(const GemvJob& job, int N, int b, int n, float v) {
+    v = apply_act(v, job.act);
+    if (GATED) v *= bf16_to_f32(job.gate[(size_t)b * N + n]);
+    if (job.res) v += bf16_to_f32(job.res[(size_t)b * N + n]);
+    job.y[(size_t)b * N + n] = (uint16_t)f32_to_bf16_bits(v);
 }
 
 DEVFN void unpack8(const uint4& u, float* f) {
@@ -139,7 +153,7 @@ DEVFN void long_rows_acc(const GemvJob& job, int B, int row0, int lane, int c_be
     }
 }
 
-template <int BB, typename F>
+template <int BB, bool GATED = false, typename F>
 DEVFN void long_rows(const GemvJob& job, int B, int row0, int lane, uint4 (&first)[GV_R][GV_U], F&& input) {
     constexpr int R = GV_R;
     const int N = job.N;
@@ -152,11 +166,7 @@ DEVFN void long_rows(const GemvJob& job, int B, int row0, int lane, uint4 (&firs
         for (int b = 0; b < BB; ++b) {
             if (b < B) {
                 float v = group_sum<6>(acc[r][b]);
-                if (lane == 0 && n < N) {
-                    v = apply_act(v, job.act);
-                    if (job.res) v += bf16_to_f32(job.res[(size_t)b * N + n]);
-                    job.y[(size_t)b * N + n] = (uint16_t)f32_to_bf16_bits(v);
-                }
+                if (lane == 0 && n < N) emit<GATED>(job, N, b, n, v);
             }
         }
     }
@@ -169,6 +179,7 @@ DEVFN int find_job(const GemvArgs& a) {
     return j;
 }
 
+template <bool GATED>
 __global__ __launch_bounds__(GV_THREADS) void gemv_multi_kernel(GemvArgs a) {
     float* xs = reinterpret_cast<float*>(dyn_lds());                    // [B][K], short-row jobs only
     const GemvJob job = a.job[find_job(a)];
@@ -196,17 +207,13 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_multi_kernel(GemvArgs a) {
         __syncthreads();
         if (threadIdx.x < GV_R * GV_MAX_B) {
             const int r = threadIdx.x / GV_MAX_B, b = threadIdx.x % GV_MAX_B, n = row0 + r;
-            if (b < B && n < N) {
-                float v = apply_act(part[0][r][b] + part[1][r][b] + part[2][r][b] + part[3][r][b], job.act);
-                if (job.res) v += bf16_to_f32(job.res[(size_t)b * N + n]);
-                job.y[(size_t)b * N + n] = (uint16_t)f32_to_bf16_bits(v);
-            }
+            if (b < B && n < N) emit<GATED>(job, N, b, n, part[0][r][b] + part[1][r][b] + part[2][r][b] + part[3][r][b]);
         }
     } else if (kchunks >= GV_LONG_KCHUNKS) {
         const int row0 = ((int)blockIdx.x - job.wg_begin) * GV_LONG_ROWS_PER_WG + wave * GV_R;
         uint4 first[GV_R][GV_U];
         load_batch(job, row0, lane, kchunks, first);
-        long_rows<GV_MAX_B>(job, B, row0, lane, first, [&](int b, int c, float* xv) {
+        long_rows<GV_MAX_B, GATED>(job, B, row0, lane, first, [&](int b, int c, float* xv) {
             unpack8(*reinterpret_cast<const uint4*>(job.x + (size_t)b * K + c * 8), xv);
         });
     } else {
@@ -239,11 +246,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_multi_kernel(GemvArgs a) {
                     float v = acc[b];                    // all-reduce inside the G-lane group (G is uniform)
                     v = G >= 32 ? group_sum<5>(v) : G >= 16 ? group_sum<4>(v) : G >= 8 ? group_sum<3>(v)
                       : G >= 4 ? group_sum<2>(v) : G >= 2 ? group_sum<1>(v) : v;
-                    if (gl == 0 && live) {
-                        v = apply_act(v, job.act);
-                        if (job.res) v += bf16_to_f32(job.res[(size_t)b * N + n]);
-                        job.y[(size_t)b * N + n] = (uint16_t)f32_to_bf16_bits(v);
-                    }
+                    if (gl == 0 && live) emit<GATED>(job, N, b, n, v);
                 }
             }
         }
@@ -348,7 +351,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_ln_kernel(GemvArgs a) {
 
 int launch(int n_jobs, int B, const void* const* W, const void* const* x, const void* const* res, const void* const* mu,
            void* const* y, const int* N, const int* K, const int* act, const LnFold* ln, const void* copy_src,
-           void* copy_dst, long copy_elems, void* stream) {
+           void* copy_dst, long copy_elems, void* stream, const void* const* gate = nullptr) {
     if (n_jobs <= 0 || n_jobs > GV_MAX_JOBS || B <= 0 || B > GV_MAX_B || !W || !x || !y || !N || !K || !act) return VRWKV_EINVAL;
     if (copy_elems < 0 || (copy_elems > 0 && (!copy_src || !copy_dst))) return VRWKV_EINVAL;
     if (copy_elems % 8 != 0) return VRWKV_ESHAPE;
@@ -367,8 +370,10 @@ int launch(int n_jobs, int B, const void* const* W, const void* const* x, const 
             if (!mu || !mu[j]) return VRWKV_EINVAL;
             if (reinterpret_cast<uintptr_t>(mu[j]) & 15u) return VRWKV_EALIGN;
         }
+        if (gate && !gate[j]) return VRWKV_EINVAL;
         a.job[j] = GemvJob{(const uint16_t*)W[j], (const uint16_t*)x[j], res ? (const uint16_t*)res[j] : nullptr,
-                           ln ? (const uint16_t*)mu[j] : nullptr, (uint16_t*)y[j], N[j], K[j], act[j], wg};
+                           ln ? (const uint16_t*)mu[j] : nullptr, gate ? (const uint16_t*)gate[j] : nullptr, (uint16_t*)y[j], N[j], K[j],
+                           act[j], wg};
         const int rows = ln ? GV_LONG_ROWS_PER_WG : long_rows ? long_rows_per_wg(K[j]) : GV_ROWS_PER_WG;
         wg += (N[j] + rows - 1) / rows;
         if (!long_rows) kmax = K[j] > kmax ? K[j] : kmax;
@@ -383,7 +388,8 @@ int launch(int n_jobs, int B, const void* const* W, const void* const* x, const 
         else if (B == 2) { if (wide) hipLaunchKernelGGL((gemv_ln_kernel<2, 2>), g, t, l, st, a); else hipLaunchKernelGGL((gemv_ln_kernel<1, 2>), g, t, l, st, a); }
         else { if (wide) hipLaunchKernelGGL((gemv_ln_kernel<2, 4>), g, t, l, st, a); else hipLaunchKernelGGL((gemv_ln_kernel<1, 4>), g, t, l, st, a); }
     }
-    else hipLaunchKernelGGL(gemv_multi_kernel, dim3((unsigned)wg), dim3(GV_THREADS), lds, (hipStream_t)stream, a);
+    else if (gate) hipLaunchKernelGGL(gemv_multi_kernel<true>, dim3((unsigned)wg), dim3(GV_THREADS), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(gemv_multi_kernel<false>, dim3((unsigned)wg), dim3(GV_THREADS), lds, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? VRWKV_OK : (int)e;
 }
@@ -399,6 +405,13 @@ extern "C" int vrwkv_gemv_multi_copy_bf16(int n_jobs, int B, const void* const* 
                                           void* const* y, const int* N, const int* K, const int* act, const void* copy_src,
                                           void* copy_dst, long copy_elems, void* stream) {
     return launch(n_jobs, B, W, x, res, nullptr, y, N, K, act, nullptr, copy_src, copy_dst, copy_elems, stream);
+}
+
+extern "C" int vrwkv_gemv_gated_copy_bf16(int n_jobs, int B, const void* const* W, const void* const* x, const void* const* res,
+                                          const void* const* gate, void* const* y, const int* N, const int* K, const int* act,
+                                          const void* copy_src, void* copy_dst, long copy_elems, void* stream) {
+    if (!gate) return VRWKV_EINVAL;
+    return launch(n_jobs, B, W, x, res, nullptr, y, N, K, act, nullptr, copy_src, copy_dst, copy_elems, stream, gate);
 }
 
 extern "C" int vrwkv_gemv_ln_multi_bf16(int n_jobs, int B, int K, const void* const* W, const void* x, const void* ln_w,

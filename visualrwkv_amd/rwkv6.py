@@ -23,6 +23,27 @@ def time_shift(x):
     return F.pad(x, (0, 0, 1, -1))
 
 
+def _behind(prev, x):
+    """The carried row `prev` (B,C) put in front of x (B,T,C): the stateful paths run the modules' own shift code over T + 1 rows and
+    drop the first, whose shift read the zero pad."""
+    return torch.cat((prev.unsqueeze(1).to(x.dtype), x), dim=1)
+
+
+class RWKV6State:
+    """Recurrent state of an RWKV-6 stack for stateful generation (the reference re-runs the whole text pass per generated token,
+    v6.xx/src/model.py:468-495).  Per layer: the last ln1 / ln2 rows the time-mix and channel-mix shifts read (the reference's ZeroPad2d
+    shift sees zeros before the first token) and the WKV state S (B,H,64,64) fp32 [key][value], the layout of RUN_CUDA_RWKV6_STATE."""
+
+    def __init__(self, args, batch, device, dtype=torch.bfloat16):
+        L, C = args.n_layer, args.n_embd
+        self.att_x = [torch.zeros(batch, C, device=device, dtype=dtype) for _ in range(L)]
+        self.ffn_x = [torch.zeros(batch, C, device=device, dtype=dtype) for _ in range(L)]
+        self.S = [torch.zeros(batch, args.dim_att // args.head_size_a, args.head_size_a, args.head_size_a, device=device, dtype=torch.float32)
+                  for _ in range(L)]
+        self.fresh = [True] * L                 # kept for rwkv7.GraphDecoder, which saves and restores it; WKV6 starts from S whatever it holds
+        self.n_tokens = 0
+
+
 class RWKV_Tmix_x060(nn.Module):
     """RWKV-6 time-mix with the 5-way data-dependent token-shift LoRA (model.py:92-194)."""
 
@@ -109,6 +130,20 @@ class RWKV_Tmix_x060(nn.Module):
         y = self.ln_x(y.view(B * T, C)).view(B, T, C)
         return self.output(y * g), state
 
+    @torch.no_grad()
+    def forward_stateful(self, x, state, wkv=None):
+        """forward_state continuing from `state` (an RWKV6State), any T: the shift's first row is the carried one, the WKV starts from the
+        carried S; both are replaced in place.  Plain module glue around RUN_CUDA_RWKV6_STATE (or `wkv`, same signature)."""
+        B, T, C = x.size()
+        lid = self.layer_id
+        r, k, v, g, w = [t[:, 1:].contiguous() for t in self.mix(_behind(state.att_x[lid], x))]
+        state.att_x[lid].copy_(x[:, -1])
+        run = wkv if wkv is not None else _wkv6.RUN_CUDA_RWKV6_STATE
+        y, S = run(B, T, C, self.n_head, r, k, v, w, self.time_faaaa, state.S[lid])
+        state.S[lid].copy_(S)
+        y = self.ln_x(y.view(B * T, C)).view(B, T, C)
+        return self.output(y * g)
+
 
 class RWKV_CMix_x060(nn.Module):
     """RWKV-6 channel-mix with the receptance gate (model.py:198-226)."""
@@ -137,6 +172,14 @@ class RWKV_CMix_x060(nn.Module):
         xr = x + xx * self.time_maa_r
         k = torch.relu(self.key(xk)) ** 2
         return torch.sigmoid(self.receptance(xr)) * self.value(k)
+
+    @torch.no_grad()
+    def forward_stateful(self, x, state):
+        """forward with the shift's first row read from `state` (an RWKV6State), which then carries x's last row."""
+        lid = self.layer_id
+        y = self.forward(_behind(state.ffn_x[lid], x))[:, 1:]
+        state.ffn_x[lid].copy_(x[:, -1])
+        return y
 
 
 class Block(nn.Module):
@@ -177,6 +220,14 @@ class Block(nn.Module):
         x = x + xx
         x = x + self.ffn(self.ln2(x))
         return x, state
+
+    @torch.no_grad()
+    def forward_stateful(self, x, state, wkv=None):
+        """Block.forward on x (B,T,C) continuing from `state` (an RWKV6State, advanced in place): the module path of stateful inference."""
+        if self.layer_id == 0:
+            x = self.ln0(x)
+        x = x + self.att.forward_stateful(self.ln1(x), state, wkv)
+        return x + self.ffn.forward_stateful(self.ln2(x), state)
 
 
 class RWKV(nn.Module):
@@ -227,3 +278,51 @@ class RWKV(nn.Module):
                 x_emb, state = block.forward_state(x_emb, None, wkv)
                 x, _ = block.forward_state(x, state, wkv, False)
         return self.ln_out(x)
+
+    @torch.no_grad()
+    def forward_stateful(self, x, state=None, last_only=False, wkv=None):
+        """Inference on embedded tokens x (B,T,C) continuing from `state` (None: empty context, zero WKV states).  Logits equal those
+        `forward` gives for the same positions of the concatenated sequence; WKV6 takes any T, so nothing is padded.  One token on the GPU
+        with args.fused goes through the batched-GEMV step (decode6.py); everything else through the module path around
+        RUN_CUDA_RWKV6_STATE (`wkv`: a callable with its signature; tests pass the oracle).  Returns (logits (B,T,V), or (B,V) with
+        last_only; state)."""
+        if state is None:
+            state = RWKV6State(self.args, x.size(0), x.device, x.dtype)
+        use_decode = False
+        if getattr(self.args, "fused", False) and x.shape[1] == 1 and wkv is None:
+            from . import decode6
+            use_decode = decode6.supported(x) and self.head.weight.dtype == torch.bfloat16
+        for block in self.blocks:
+            x = decode6.block_decode(block, x, state) if use_decode else block.forward_stateful(x, state, wkv)
+        state.n_tokens += x.size(1)
+        state.fresh = [False] * len(state.fresh)
+        if use_decode:
+            logits = decode6.head_decode(self, x)
+            return (logits if last_only else logits.unsqueeze(1)), state
+        if last_only:
+            x = x[:, -1]
+        return self.head(self.ln_out(x)), state
+
+    def make_decoder(self, state):
+        """A single-token decode step captured in a HIP graph on one stream (the step is a chain: the graph has no parallel branches).
+        Returns `step(x_emb (B,1,C)) -> logits (B,V)`; `state` is advanced in place by every call, exactly as
+        `forward_stateful(x_emb, state, last_only=True)` would."""
+        from .rwkv7 import GraphDecoder
+        return GraphDecoder(self, state)
+
+    def decoder_for(self, state):
+        """`make_decoder` with the captured graph re-used across prompts: one capture per (batch size, device, parameter versions);
+        later calls copy `state` into the graph's own state tensors (GraphDecoder.load_state).  The returned decoder advances ITS state
+        (`decoder.state`), not the argument."""
+        from . import param_state
+        from .rwkv7 import GraphDecoder
+        S0 = state.S[0]
+        key = (S0.shape[0], S0.device, sum(p._version for p in self.parameters()), param_state.generation())
+        cache = self.__dict__.setdefault("_decoders", {})
+        dec = cache.get(key)
+        if dec is None:
+            cache.clear()                                 # parameters changed (or first use): stale graphs go
+            dec = cache[key] = GraphDecoder(self, state)
+        elif dec.state is not state:
+            dec.load_state(state)
+        return dec

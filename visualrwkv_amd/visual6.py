@@ -83,8 +83,8 @@ class VisualRWKV6(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx, wkv=None):
         """Greedy generation of one sample in image-state mode (v6.xx model.py:468-495, which calls a method that file does not have: this
-        is its intent).  The per-layer image states are computed once; the text pass is re-run from them for every new token (a stateful
-        RWKV-6 decode step is not built)."""
+        is its intent).  The per-layer image states are computed once; the text pass is re-run from them for every new token
+        (`generate_stateful` carries the state instead: one row per new token, and both models)."""
         if not getattr(self.args, "image_state", 0):
             raise NotImplementedError("generate is built for args.image_state = 1")
         if do_sample:
@@ -99,6 +99,57 @@ class VisualRWKV6(nn.Module):
             if generated[-1] == stop_token_idx:
                 break
             x = torch.cat((x, self.rwkv.emb(next_token)), dim=-2)[:, -self.args.ctx_len:, :]
+        return generated
+
+    @torch.no_grad()
+    def prefill_state(self, input_ids, images, wkv=None):
+        """The prompt's pass for stateful generation: -> (logits of the last row (1,V), an RWKV6State behind the whole prompt).
+        image_state = 1: the image pass gives every layer's S, the shift rows start at zero (v6.xx has no shift across the image / text
+        boundary), one pass over the text from there.  image_state = 0: `bidirectional_forward` over the prompt, keeping what every layer
+        ends in -- on odd layers that is the state behind the flipped image span and the text after it; what follows the span is causal
+        in every layer, so the steps after this are the plain ones."""
+        from .rwkv6 import RWKV6State
+        samples = {"input_ids": input_ids, "images": images, "labels": torch.full_like(input_ids, IGNORE_INDEX)}
+        if getattr(self.args, "image_state", 0):
+            x, _, image_features = self.preparing_embedding_state(samples, truncate=False)
+            state = RWKV6State(self.args, x.size(0), x.device, x.dtype)
+            for S, s_img in zip(state.S, self.image_states(image_features, wkv)):
+                S.copy_(s_img)
+            logits, state = self.rwkv.forward_stateful(x, state, last_only=True, wkv=wkv)
+            return logits, state
+        x, _, _ = self.preparing_embedding(samples, truncate=False)
+        state = RWKV6State(self.args, x.size(0), x.device, x.dtype)
+        s, e = self.img_start, self.img_end
+        for i, block in enumerate(self.rwkv.blocks):
+            rev = i % 2 == 1
+            if rev:
+                x = torch.cat((x[:, :s], x[:, s:e].flip(1), x[:, e:]), dim=1)
+            x = block.forward_stateful(x, state, wkv)
+            if rev:
+                x = torch.cat((x[:, :s], x[:, s:e].flip(1), x[:, e:]), dim=1)
+        state.n_tokens = x.size(1)
+        return self.rwkv.head(self.rwkv.ln_out(x[:, -1])), state
+
+    @torch.no_grad()
+    def generate_stateful(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx, use_graph=None, wkv=None):
+        """`generate` with a carried state, for both models: one pass over the prompt (`prefill_state`), then one token per step -- a new
+        token costs one row, not a pass over everything before it.  Returns what `generate` returns (the context is not cut to ctx_len:
+        the state has no window).  use_graph: replay the step from a captured HIP graph (`RWKV.decoder_for`); None = where the decode
+        step runs (bf16 on the GPU with args.fused)."""
+        if do_sample:
+            raise NotImplementedError
+        logits, state = self.prefill_state(input_ids, images, wkv)
+        if use_graph is None:
+            use_graph = bool(getattr(self.args, "fused", False)) and wkv is None and logits.is_cuda and logits.dtype == torch.bfloat16
+        step = self.rwkv.decoder_for(state) if use_graph else \
+            (lambda x_emb: self.rwkv.forward_stateful(x_emb, state, last_only=True, wkv=wkv)[0])
+        generated = []
+        for i in range(max_new_tokens):
+            next_token = torch.argmax(logits, dim=-1, keepdim=True)
+            generated.append(next_token.item())
+            if generated[-1] == stop_token_idx or i == max_new_tokens - 1:
+                break
+            logits = step(self.rwkv.emb(next_token))
         return generated
 
     def bidirectional_forward(self, x, wkv=None):
