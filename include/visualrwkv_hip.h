@@ -574,6 +574,13 @@ long vrwkv_wgrad_skinny_ws_floats(long M, int Nw, int D);
 int vrwkv_wgrad_skinny_bf16(long M, int Nw, int D, const void* wide, const void* narrow, void* out, int transposed,
                             float* ws, void* stream);
 
+/* Write-wide product of a LoRA pair: out (M,C) = a (M,R) . w with w (R,C) row-major (w_is_CxR == 0: h @ w2 of the forward), or
+ * out = a . w^T with w (C,R) row-major (w_is_CxR != 0: the input gradient dh @ w1^T of a down-projection) -- VisualRWKV-v7/v7.00/src/model.py:176,
+ * 181-183 and autograd's mm.  bf16 operands, fp32 accumulation, one rounding.  csrc/skinny_up.h: w stays in registers as MFMA fragments, the
+ * output leaves as row-contiguous 16-byte stores.  R in {32,64,96,128,160,256}, C % 128 == 0 (VRWKV_ESHAPE otherwise), any M >= 1 (rows
+ * past M and bytes behind out are not touched); all pointers 16-byte aligned. */
+int vrwkv_skinny_up_bf16(long M, int R, int C, const void* a, const void* w, int w_is_CxR, void* out, void* stream);
+
 /* ---- Weight gradient of a square / wide projection: out (N1 x N2, bf16) = A^T B for A (M x N1), B (M x N2) bf16 row-major, fp32
  * accumulation (dW = dy^T x of nn.Linear: VisualRWKV-v7/v7.00/src/model.py:150-153 receptance / key / value / output, :214-215
  * channel-mix key / value, :281 head; autograd's dy.t().mm(x)).  csrc/wgrad_big.h: both MFMA operands by transposing LDS reads from

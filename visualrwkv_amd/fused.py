@@ -89,19 +89,57 @@ def wgrad_skinny(x2d, dy2d):
     return out
 
 
+LORA_UP = os.environ.get("VRWKV_LORA_UP", "1") != "0"            # A/B switch: 0 = the library's GEMM for the write-wide products a (M, r) . w -> (M, C)
+SKINNY_UP_RANKS = (32, 64, 96, 128, 160, 256)
+# (rank, w_is_CxR) pairs that run on csrc/skinny_up.h: the ones that beat the library's best kernel for the shape by more than 10 % at M = 41 984,
+# C = 2048 (benchmarks/lora_gemm_micro.py); a pair that does not stays on the library.  profiles/skinny_up_micro.jsonl: all twelve do, by 32 %
+# (r = 256, w as C x r) to 107 %, with bit-equal results.
+SKINNY_UP_CASES = frozenset((r, l) for r in SKINNY_UP_RANKS for l in (0, 1))
+
+
+def skinny_up_supported(a2d, w, w_is_CxR):
+    """a2d (M, R) . w (R, C), or a2d . w^T for w (C, R) with w_is_CxR: whether csrc/skinny_up.h takes it."""
+    if not (LORA_UP and a2d.dim() == 2 and w.dim() == 2 and a2d.is_cuda and w.is_cuda and a2d.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+            and a2d.is_contiguous() and w.is_contiguous() and a2d.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0):
+        return False
+    R = a2d.shape[1]
+    C, Rw = (w.shape[0], w.shape[1]) if w_is_CxR else (w.shape[1], w.shape[0])
+    return Rw == R and (R, int(bool(w_is_CxR))) in SKINNY_UP_CASES and C % 128 == 0 and C > R and a2d.shape[0] >= 1
+
+
+def skinny_up(a2d, w, w_is_CxR):
+    """The write-wide product of a LoRA pair on csrc/skinny_up.h.  Returns (M, C) bf16."""
+    M, R = a2d.shape
+    C = w.shape[0] if w_is_CxR else w.shape[1]
+    out = torch.empty(M, C, dtype=torch.bfloat16, device=a2d.device)
+    rc = hip_lib.load().vrwkv_skinny_up_bf16(M, R, C, a2d.data_ptr(), w.data_ptr(), int(bool(w_is_CxR)), out.data_ptr(), _stream(a2d))
+    hip_lib.check(rc, "vrwkv_skinny_up_bf16")
+    return out
+
+
+def _lora_product(a, w, w_is_CxR):
+    """a @ w (w_is_CxR = 0) or a @ w.t(): the own kernel for the write-wide shapes it takes, the library for everything else."""
+    if LORA_UP and a.is_cuda and a.is_contiguous():
+        a2d = a.view(-1, a.shape[-1])
+        if skinny_up_supported(a2d, w, w_is_CxR):
+            return skinny_up(a2d, w, w_is_CxR).view(*a.shape[:-1], -1)
+    return a @ w.t() if w_is_CxR else a @ w
+
+
 class _LoraMM(torch.autograd.Function):
-    """x @ w for a LoRA factor w (C x rank or rank x C): library GEMMs for the output and the input gradient, the
-    skinny weight-gradient kernel for dw (src/model.py:176,181-183 -- plain `@` in the reference)."""
+    """x @ w for a LoRA factor w (C x rank or rank x C): csrc/skinny_up.h for the write-wide output (w rank x C) and the write-wide
+    input gradient (w C x rank), library GEMMs for the read-wide ones, the skinny weight-gradient kernel for dw
+    (src/model.py:176,181-183 -- plain `@` in the reference)."""
 
     @staticmethod
     def forward(ctx, x, w):
         ctx.save_for_backward(x, w)
-        return x @ w
+        return _lora_product(x, w, 0)
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        dx = dy @ w.t() if ctx.needs_input_grad[0] else None
+        dx = _lora_product(dy, w, 1) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
             x2d, dy2d = x.reshape(-1, x.shape[-1]), dy.reshape(-1, dy.shape[-1])

@@ -112,6 +112,7 @@ PROTOTYPES = {
     "vrwkv_wkv7_profile_bf16": (_c_int, [_c_int] * 4 + [_c_void_p] * 18),
     "vrwkv_wgrad_skinny_ws_floats": (_c_long, [_c_long, _c_int, _c_int]),
     "vrwkv_wgrad_skinny_bf16": (_c_int, [_c_long, _c_int, _c_int] + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 2),
+    "vrwkv_skinny_up_bf16": (_c_int, [_c_long, _c_int, _c_int] + [_c_void_p] * 2 + [_c_int] + [_c_void_p] * 2),
     "vrwkv_wgrad_big_ws_floats": (_c_long, [_c_long, _c_int, _c_int]),
     "vrwkv_wgrad_big_bf16": (_c_int, [_c_long, _c_int, _c_int] + [_c_void_p] * 5),
     "vrwkv_patch_embed_wgrad_ws_floats": (_c_long, [_c_int] * 5),
