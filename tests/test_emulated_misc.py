@@ -1,7 +1,8 @@
 """csrc/fused_ops.hip (AdamW / squared norm), csrc/loss_fused.hip (cross-entropy + L2Wrap) and csrc/visual_ops.hip (adaptive pool,
 context gate) compiled whole for the host lockstep emulator: the product's vrwkv_* entry points on CPU tensors, against torch.
 The GPU suite holds the same comparisons on the device (tests/test_optim_gpu.py, test_fused_gpu.py, test_visual_gpu.py); these run
-without one."""
+without one.  Per row and per element at the kernels' edges, on the emulator and on the device with the same bodies: tests/test_head_shapes.py
+(loss_fused.hip) and tests/test_optim_shapes.py (AdamW, squared norm)."""
 import ctypes
 
 import pytest

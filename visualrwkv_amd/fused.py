@@ -180,7 +180,7 @@ BIG_WGRAD = os.environ.get("VRWKV_BIG_WGRAD", "1") != "0"        # A/B switch: 0
 
 def wgrad_big_supported(dy2d, x2d):
     return (BIG_WGRAD and dy2d.is_cuda and dy2d.dtype == torch.bfloat16 and x2d.dtype == torch.bfloat16 and dy2d.is_contiguous()
-            and x2d.is_contiguous() and dy2d.shape[0] % 32 == 0 and dy2d.shape[1] % 256 == 0 and x2d.shape[1] % 256 == 0
+            and x2d.is_contiguous() and dy2d.shape[0] > 0 and dy2d.shape[0] % 32 == 0 and dy2d.shape[1] % 256 == 0 and x2d.shape[1] % 256 == 0
             and max(dy2d.shape[1], x2d.shape[1]) <= 16384)      # the head (65 536 x 2048): the library is 4 % faster (profiles/r4_wgrad_big_micro.jsonl)
 
 
