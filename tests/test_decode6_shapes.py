@@ -452,22 +452,30 @@ def _untouched(*bufs):
         assert bool(torch.isnan(b.float()).all()), "a rejected call wrote to an output"
 
 
+# The refusal tables are read off the entries as they stand: every count at 0 and one past its cap, every width just off its modulus,
+# every pointer NULL in turn and 2 bytes (fp32: 4) off a 16-byte boundary; the gated GEMV alone has pointers it does not check (gate,
+# res, y: element accesses), shown by an accepted call.  "Two faults" expect the code of the check that comes first.
 # every buffer holds 5 batch rows: no case depends on being refused to stay in bounds
 @pytest.mark.parametrize("backend", _params([()]))
 def test_rejects_step(backend, be):
     g = be.gen(61)
     B, H = 2, 2
-    r, k, v, w, u = [rnd(be, g, 5 * H * 64 + 8) for _ in range(5)]
-    y, state = _nan_like(be, 5 * H * 64 + 8), _nan_like(be, 5 * H * 4096 + 4, dtype=torch.float32)
+    names = ("r", "k", "v", "w", "u", "state", "y")
+    t = {n: rnd(be, g, 5 * H * 64 + 8) for n in names[:5]}
+    t["y"], t["state"] = _nan_like(be, 5 * H * 64 + 8), _nan_like(be, 5 * H * 4096 + 4, dtype=torch.float32)
+    y, state = t["y"], t["state"]
 
-    def go(B=B, H=H, r=r.data_ptr(), st=state.data_ptr(), y=y.data_ptr(), u=u.data_ptr()):
-        return rc_of(be, "vrwkv_wkv6_step_bf16", STEP_ARGT, B, H, VP(r), P(k), P(v), P(w), VP(u), VP(st), VP(y))
+    def go(B=B, H=H, null=(), off=()):
+        ad = [VP(0 if n in null else t[n].data_ptr() + ((4 if n == "state" else 2) if n in off else 0)) for n in names]
+        return rc_of(be, "vrwkv_wkv6_step_bf16", STEP_ARGT, B, H, *ad)
 
     assert go(B=0) == EINVAL and go(B=5) == EINVAL and go(H=0) == EINVAL
-    assert go(r=None) == EINVAL and go(st=None) == EINVAL and go(y=None) == EINVAL
     assert go(H=129) == ESHAPE                                                  # C = 8256
-    assert go(r=r.data_ptr() + 2) == EALIGN and go(st=state.data_ptr() + 4) == EALIGN and go(y=y.data_ptr() + 2) == EALIGN
-    assert go(u=u.data_ptr() + 2) == EALIGN
+    for name in names:
+        assert go(null=(name,)) == EINVAL, name
+        assert go(off=(name,)) == EALIGN, name
+    # two faults
+    assert go(B=5, H=129) == EINVAL and go(H=129, null=("r",)) == EINVAL and go(H=129, off=("r",)) == ESHAPE
     _untouched(y, state)
     state.zero_()
     assert go() == 0
@@ -484,17 +492,23 @@ def test_rejects_ddlerp(backend, be):
     maa = [rnd(be, g, C + 8) for _ in range(5)]
     outs = [_nan_like(be, 5 * C + 8) for _ in range(5)]
 
-    def go(B=B, C=C, D=D, h=h.data_ptr(), prev=prev.data_ptr(), maa=maa, outs=outs, w2=w2.data_ptr()):
-        return rc_of(be, "vrwkv_decode6_ddlerp_bf16", DD_ARGT, B, C, D, VP(h), VP(prev), P(hid), VP(w2), arr(maa) if maa is not None else None,
+    def go(B=B, C=C, D=D, h=h.data_ptr(), prev=prev.data_ptr(), maa=maa, outs=outs, w2=w2.data_ptr(), hid=hid.data_ptr()):
+        return rc_of(be, "vrwkv_decode6_ddlerp_bf16", DD_ARGT, B, C, D, VP(h), VP(prev), VP(hid), VP(w2), arr(maa) if maa is not None else None,
                      arr(outs) if outs is not None else None)
 
     assert go(B=0) == EINVAL and go(B=5) == EINVAL
     assert go(C=72) == ESHAPE and go(C=0) == ESHAPE and go(C=8256) == ESHAPE
     assert go(D=48) == ESHAPE and go(D=0) == ESHAPE and go(D=128) == ESHAPE
     assert go(h=None) == EINVAL and go(prev=None) == EINVAL and go(maa=None) == EINVAL and go(outs=None) == EINVAL
+    assert go(hid=None) == EINVAL and go(w2=None) == EINVAL
     assert go(maa=maa[:2] + [None] + maa[3:]) == EINVAL and go(outs=outs[:4] + [None]) == EINVAL
     assert go(h=h.data_ptr() + 2) == EALIGN and go(prev=prev.data_ptr() + 2) == EALIGN and go(w2=w2.data_ptr() + 2) == EALIGN
+    assert go(hid=hid.data_ptr() + 2) == EALIGN
     assert go(outs=outs[:3] + [outs[3].data_ptr() + 2] + outs[4:]) == EALIGN and go(maa=[maa[0].data_ptr() + 2] + maa[1:]) == EALIGN
+    # two faults
+    assert go(B=5, C=72) == EINVAL and go(C=72, h=h.data_ptr() + 2) == ESHAPE and go(h=None, D=48) == EINVAL
+    assert go(maa=maa[:2] + [None] + maa[3:], h=h.data_ptr() + 2) == EINVAL
+    assert go(maa=[maa[0].data_ptr() + 2] + maa[1:], outs=outs[:4] + [None]) == EINVAL      # a NULL anywhere in the arrays before any alignment
     _untouched(*outs)
     assert torch.equal(bits(prev), bits(keep)), "a rejected call replaced the carried row"
     assert go() == 0
@@ -506,17 +520,22 @@ def test_rejects_tmix6_head(backend, be):
     g = be.gen(63)
     B, H = 2, 2
     p = head_inputs(be, g, 5, H, 128)
-    out, state = _nan_like(be, 5 * H * 64 + 8), _nan_like(be, 5 * H * 4096 + 4, dtype=torch.float32)
+    names = ("r", "k", "v", "g", "hid", "w2", "td", "u", "ln_w", "ln_b", "state", "out")
+    t = {n: p[n] for n in names[:10]}
+    t["out"], t["state"] = _nan_like(be, 5 * H * 64 + 8), _nan_like(be, 5 * H * 4096 + 4, dtype=torch.float32)
+    out, state = t["out"], t["state"]
 
-    def go(B=B, H=H, Dd=64, r=p["r"].data_ptr(), w2=p["w2"].data_ptr(), st=state.data_ptr(), out=out.data_ptr()):
-        return rc_of(be, "vrwkv_decode6_tmix_head_bf16", HEAD_ARGT, B, H, Dd, VP(r), P(p["k"]), P(p["v"]), P(p["g"]), P(p["hid"]), VP(w2),
-                     P(p["td"]), P(p["u"]), P(p["ln_w"]), P(p["ln_b"]), EPS_GN, VP(st), VP(out))
+    def go(B=B, H=H, Dd=64, null=(), off=()):
+        ad = [VP(0 if n in null else t[n].data_ptr() + ((4 if n == "state" else 2) if n in off else 0)) for n in names]
+        return rc_of(be, "vrwkv_decode6_tmix_head_bf16", HEAD_ARGT, B, H, Dd, *ad[:10], EPS_GN, *ad[10:])
 
     assert go(B=0) == EINVAL and go(B=5) == EINVAL and go(H=0) == EINVAL
-    assert go(Dd=96) == ESHAPE and go(Dd=32) == ESHAPE and go(Dd=256) == ESHAPE and go(H=129) == ESHAPE
-    assert go(r=None) == EINVAL and go(w2=None) == EINVAL and go(st=None) == EINVAL and go(out=None) == EINVAL
-    assert go(r=p["r"].data_ptr() + 2) == EALIGN and go(w2=p["w2"].data_ptr() + 2) == EALIGN
-    assert go(st=state.data_ptr() + 4) == EALIGN and go(out=out.data_ptr() + 2) == EALIGN
+    assert go(Dd=96) == ESHAPE and go(Dd=32) == ESHAPE and go(Dd=256) == ESHAPE and go(Dd=0) == ESHAPE and go(H=129) == ESHAPE
+    for name in names:
+        assert go(null=(name,)) == EINVAL, name
+        assert go(off=(name,)) == EALIGN, name
+    # two faults
+    assert go(B=5, Dd=96) == EINVAL and go(Dd=96, null=("w2",)) == EINVAL and go(Dd=96, off=("r",)) == ESHAPE and go(H=129, off=("state",)) == ESHAPE
     _untouched(out, state)
 
 
@@ -524,20 +543,34 @@ def test_rejects_tmix6_head(backend, be):
 def test_rejects_gemv_gated(backend, be):
     g = be.gen(64)
     B, N, K = 2, 9, 64
-    W, x, gate, y = rnd(be, g, N + 1, K), rnd(be, g, 5 + 1, K), rnd(be, g, 5, N), _nan_like(be, 5, N)
+    W, x, gate, y, res = rnd(be, g, N + 1, K), rnd(be, g, 5 + 1, K), rnd(be, g, 5 + 1, N), _nan_like(be, 5 + 1, N), rnd(be, g, 5 + 1, N)
     src, dst = rnd(be, g, 64), _nan_like(be, 64)
 
-    def go(n=1, B=B, W=W.data_ptr(), N=N, K=K, gate=[gate], s=None, d=None, elems=0):
+    def go(n=1, B=B, W=W.data_ptr(), x=x.data_ptr(), y=y.data_ptr(), res=None, N=N, K=K, gate=[gate], null=(), s=None, d=None, elems=0):
         m = max(n, 1)
-        return rc_of(be, "vrwkv_gemv_gated_copy_bf16", GATED_ARGT, n, B, arr([W] * m), arr([x] * m), None, arr(gate * m) if gate is not None else None,
-                     arr([y] * m), ints([N] * m), ints([K] * m), ints([0] * m), VP(s), VP(d), elems)
+        a = dict(W=arr([W] * m), x=arr([x] * m), res=arr([res] * m) if res is not None else None, gate=arr(gate * m) if gate is not None else None,
+                 y=arr([y] * m), N=ints([N] * m), K=ints([K] * m), act=ints([0] * m))
+        return rc_of(be, "vrwkv_gemv_gated_copy_bf16", GATED_ARGT, n, B, *[None if k in null else a[k] for k in ("W", "x", "res", "gate", "y", "N", "K", "act")],
+                     VP(s), VP(d), elems)
 
+    sp, dp = src.data_ptr(), dst.data_ptr()
     assert go(n=0) == EINVAL and go(n=9) == EINVAL and go(B=0) == EINVAL and go(B=5) == EINVAL
     assert go(gate=None) == EINVAL and go(gate=[None]) == EINVAL
-    assert go(K=60) == ESHAPE and go(N=0) == ESHAPE
-    assert go(W=W.data_ptr() + 2) == EALIGN
-    assert go(s=src.data_ptr(), d=dst.data_ptr(), elems=12) == ESHAPE and go(s=None, d=dst.data_ptr(), elems=8) == EINVAL
-    assert go(s=src.data_ptr(), d=dst.data_ptr() + 2, elems=8) == EALIGN
+    for name in ("W", "x", "y", "N", "K", "act"):
+        assert go(null=(name,)) == EINVAL, name
+    assert go(W=None) == ESHAPE and go(x=None) == ESHAPE and go(y=None) == ESHAPE
+    assert go(K=60) == ESHAPE and go(K=0) == ESHAPE and go(N=0) == ESHAPE
+    assert go(W=W.data_ptr() + 2) == EALIGN and go(x=x.data_ptr() + 2) == EALIGN
+    assert go(s=sp, d=dp, elems=12) == ESHAPE and go(s=sp, d=dp, elems=-8) == EINVAL
+    assert go(s=None, d=dp, elems=8) == EINVAL and go(s=sp, d=None, elems=8) == EINVAL
+    assert go(s=sp, d=dp + 2, elems=8) == EALIGN and go(s=sp + 2, d=dp, elems=8) == EALIGN
+    # two faults: the gate array first, then the launcher's order (counts, copy side job, job by job: shape, alignment, gate)
+    assert go(gate=None, n=0) == EINVAL and go(gate=[None], K=60) == ESHAPE and go(gate=[None], W=W.data_ptr() + 2) == EALIGN
+    assert go(s=sp, d=dp, elems=12, gate=[None]) == ESHAPE and go(B=5, K=60) == EINVAL
+    _untouched(y, dst)
+    y2 = _nan_like(be, 5 + 1, N)
+    assert go(y=y2.data_ptr() + 2, res=res.data_ptr() + 2, gate=[gate.data_ptr() + 2]) == 0        # gate, res and y: element accesses, not checked
+    assert bool(torch.isfinite(y2.reshape(-1)[1:1 + B * N].float()).all()) and bool(torch.isnan(y2.reshape(-1)[1 + B * N:].float()).all())
     _untouched(y, dst)
     assert go() == 0
     assert bool(torch.isfinite(y[:B].float()).all()) and bool(torch.isnan(y[B:].float()).all())

@@ -643,53 +643,101 @@ def _untouched(*bufs):
         assert bool(torch.isnan(b.float()).all()), "a rejected call wrote to an output"
 
 
+def _pad(t, n=8):
+    """The tensor's elements followed by n spare ones: a pointer 2 bytes into it still has the whole tensor in front of it."""
+    return torch.cat([t.reshape(-1), torch.zeros(n, dtype=t.dtype, device=t.device)])
+
+
+# The refusal tables below are read off the entries as they stand: every count at 0 and one past its cap, every width just off its
+# modulus, every pointer NULL in turn, every pointer the entry checks for alignment 2 bytes off (fp32: 4), and for the pointers it does
+# not check (they are read and written by element) one accepted call with all of them 2 bytes off.  The order of the checks is part of
+# the table: the cases marked "two faults" expect the code of the check that comes first.  Every buffer has spare rows: no case depends
+# on being refused to stay in bounds.
 @pytest.mark.parametrize("backend", _params([()]))
 def test_rejects_gemv(backend, be):
     g = be.gen(3)
     B, N, K = 2, 9, 64
-    W, x, y = rnd(be, g, N + 1, K), rnd(be, g, B + 1, K), _nan_like(be, B, N)
+    W, x, y, res = rnd(be, g, N + 1, K), rnd(be, g, 5 + 1, K), _nan_like(be, 5 + 1, N), rnd(be, g, 5 + 1, N)
     src, dst = rnd(be, g, 64), _nan_like(be, 64)
     T = [I, I] + [VP] * 7
 
-    def go(n=1, B=B, W=W.data_ptr(), x=x.data_ptr(), N=N, K=K):
-        return rc_of(be, "vrwkv_gemv_multi_bf16", T, n, B, arr([W] * max(n, 1)), arr([x] * max(n, 1)), None, arr([y] * max(n, 1)),
-                     ints([N] * max(n, 1)), ints([K] * max(n, 1)), ints([0] * max(n, 1)))
+    def go(n=1, B=B, W=W.data_ptr(), x=x.data_ptr(), y=y.data_ptr(), res=None, N=N, K=K, null=(), copy=None):
+        m = max(n, 1)
+        a = dict(W=arr([W] * m), x=arr([x] * m), res=arr([res] * m) if res is not None else None, y=arr([y] * m), N=ints([N] * m), K=ints([K] * m),
+                 act=ints([0] * m))
+        args = [n, B] + [None if k in null else a[k] for k in ("W", "x", "res", "y", "N", "K", "act")]
+        if copy is None:
+            return rc_of(be, "vrwkv_gemv_multi_bf16", T, *args)
+        return rc_of(be, "vrwkv_gemv_multi_copy_bf16", T + [VP, VP, L], *args, VP(copy[0]), VP(copy[1]), copy[2])
 
-    def cp(s, d, elems):
-        return rc_of(be, "vrwkv_gemv_multi_copy_bf16", T + [VP, VP, L], 1, B, arr([W]), arr([x]), None, arr([y]), ints([N]), ints([K]), ints([0]),
-                     VP(s), VP(d), elems)
+    def cp(s, d, elems, **kw):
+        return go(copy=(s, d, elems), **kw)
 
-    assert go(n=0) == EINVAL and go(n=9) == EINVAL
-    assert go(B=0) == EINVAL and go(B=5) == EINVAL
-    assert go(K=60) == ESHAPE and go(N=0) == ESHAPE
-    assert go(W=W.data_ptr() + 2) == EALIGN and go(x=x.data_ptr() + 2) == EALIGN
-    assert cp(src.data_ptr(), dst.data_ptr(), 12) == ESHAPE
-    assert cp(None, dst.data_ptr(), 8) == EINVAL and cp(src.data_ptr(), None, 8) == EINVAL
-    assert cp(src.data_ptr() + 2, dst.data_ptr(), 8) == EALIGN and cp(src.data_ptr(), dst.data_ptr() + 2, 8) == EALIGN
+    sp, dp = src.data_ptr(), dst.data_ptr()
+    for both in (go, lambda **kw: cp(sp, dp, 8, **kw)):          # the copy entry runs the same checks on its jobs
+        assert both(n=0) == EINVAL and both(n=9) == EINVAL
+        assert both(B=0) == EINVAL and both(B=5) == EINVAL
+        for name in ("W", "x", "y", "N", "K", "act"):
+            assert both(null=(name,)) == EINVAL, name
+        assert both(W=None) == ESHAPE and both(x=None) == ESHAPE and both(y=None) == ESHAPE        # a NULL job pointer answers like a bad N or K
+        assert both(K=60) == ESHAPE and both(K=0) == ESHAPE and both(N=0) == ESHAPE
+        assert both(W=W.data_ptr() + 2) == EALIGN and both(x=x.data_ptr() + 2) == EALIGN
+        # two faults
+        assert both(B=5, K=60) == EINVAL and both(n=0, null=("W",)) == EINVAL
+        assert both(W=None, x=x.data_ptr() + 2) == ESHAPE and both(K=60, W=W.data_ptr() + 2) == ESHAPE
+    assert cp(sp, dp, 12) == ESHAPE and cp(sp, dp, -8) == EINVAL
+    assert cp(None, dp, 8) == EINVAL and cp(sp, None, 8) == EINVAL
+    assert cp(sp + 2, dp, 8) == EALIGN and cp(sp, dp + 2, 8) == EALIGN
+    assert cp(sp + 2, None, 0) == EALIGN                                   # the copy pointers are checked whatever copy_elems is
+    # two faults: the copy side job is checked after the counts and before the jobs
+    assert cp(sp, dp, 12, n=0) == EINVAL and cp(None, dp, 8, K=60) == EINVAL
+    assert cp(sp + 2, dp, 12) == ESHAPE and cp(sp, dp, 12, K=60) == ESHAPE and cp(sp, dp + 2, 8, W=None) == EALIGN
+    _untouched(y, dst)
+    y2 = _nan_like(be, 5 + 1, N)
+    assert go(y=y2.data_ptr() + 2, res=res.data_ptr() + 2) == 0            # y and res are not checked for alignment: element accesses
+    assert bool(torch.isfinite(y2.reshape(-1)[1:1 + B * N].float()).all()) and bool(torch.isnan(y2.reshape(-1)[1 + B * N:].float()).all())
     _untouched(y, dst)
     assert go() == 0                            # the same arguments without the fault are accepted
-    assert bool(torch.isfinite(y.float()).all())
+    assert bool(torch.isfinite(y[:B].float()).all())
 
 
 @pytest.mark.parametrize("backend", _params([()]))
 def test_rejects_fold(backend, be):
     g = be.gen(4)
     B, N = 2, 9
-    y, h = _nan_like(be, B, N), _nan_like(be, B, 4104)
+    y, h = _nan_like(be, 5 + 1, N), _nan_like(be, 5 + 1, 4104)
     T = [I, I, I, VP, VP, VP, VP, F32] + [VP] * 6
 
-    def go(K=512, n=1, B=B, mu=0):
-        W, x, lw, lb, prev, m = rnd(be, g, N, K), rnd(be, g, B, K), rnd(be, g, K), rnd(be, g, K), rnd(be, g, B, K), rnd(be, g, K + 8)
-        mu = [m.data_ptr() + mu if mu is not None else 0] * max(n, 1)
-        return rc_of(be, "vrwkv_gemv_ln_multi_bf16", T, n, B, K, arr([W] * max(n, 1)), P(x), P(lw), P(lb), EPS_LN, P(prev), arr(mu), P(h),
-                     arr([y] * max(n, 1)), ints([N] * max(n, 1)), ints([0] * max(n, 1)))
+    def go(K=512, n=1, B=B, N=N, mu=0, null=(), off=(), y=y, h=h):
+        Kt = max(K, 8)
+        t = dict(W=rnd(be, g, N + 1, Kt), x=rnd(be, g, 5 + 1, Kt), ln_w=rnd(be, g, Kt + 8), ln_b=rnd(be, g, Kt + 8), x_prev=rnd(be, g, 5 + 1, Kt),
+                 mu=rnd(be, g, Kt + 8), h=h, y=y)
+        ad = {k: (0 if k in null else v.data_ptr() + (2 if k in off else 0)) for k, v in t.items()}
+        m = max(n, 1)
+        ad["mu"] = 0 if mu is None else ad["mu"] + mu
+        arrays = dict(Wa=arr([ad["W"]] * m), mua=arr([ad["mu"]] * m), ya=arr([ad["y"]] * m), Na=ints([N] * m), acta=ints([0] * m))
+        arrays = {k: (None if k in null else v) for k, v in arrays.items()}
+        return rc_of(be, "vrwkv_gemv_ln_multi_bf16", T, n, B, K, arrays["Wa"], VP(ad["x"]), VP(ad["ln_w"]), VP(ad["ln_b"]), EPS_LN, VP(ad["x_prev"]),
+                     arrays["mua"], VP(ad["h"]), arrays["ya"], arrays["Na"], arrays["acta"])
 
-    assert go(K=504) == ESHAPE and go(K=4104) == ESHAPE
+    assert go(K=504) == ESHAPE and go(K=4104) == ESHAPE and go(K=516) == ESHAPE and go(K=0) == ESHAPE and go(N=0) == ESHAPE
     assert go(mu=None) == EINVAL and go(mu=2) == EALIGN
     assert go(n=0) == EINVAL and go(n=9) == EINVAL and go(B=0) == EINVAL and go(B=5) == EINVAL
+    for name in ("x", "ln_w", "ln_b", "x_prev", "h", "Wa", "mua", "ya", "Na", "acta"):
+        assert go(null=(name,)) == EINVAL, name
+    assert go(null=("W",)) == ESHAPE and go(null=("y",)) == ESHAPE
+    for name in ("W", "x", "ln_w", "ln_b", "x_prev", "h"):
+        assert go(off=(name,)) == EALIGN, name
+    # two faults: the entry's own pointers come before the launcher's counts and jobs
+    assert go(off=("ln_w",), B=0) == EALIGN and go(n=0, off=("ln_w",)) == EINVAL and go(null=("x",), off=("h",)) == EINVAL
+    assert go(K=504, mu=None) == ESHAPE and go(null=("W",), off=("x",)) == ESHAPE and go(K=4104, mu=2) == ESHAPE
+    _untouched(y, h)
+    y2, h2 = _nan_like(be, 5 + 1, N), _nan_like(be, 5 + 1, 512)
+    assert go(off=("y",), y=y2, h=h2) == 0                                 # y is not checked for alignment: element stores
+    assert bool(torch.isfinite(y2.reshape(-1)[1:1 + B * N].float()).all()) and bool(torch.isnan(y2.reshape(-1)[1 + B * N:].float()).all())
     _untouched(y, h)
     assert go() == 0
-    assert bool(torch.isfinite(y.float()).all()) and bool(torch.isfinite(h.reshape(-1)[:B * 512].float()).all())
+    assert bool(torch.isfinite(y[:B].float()).all()) and bool(torch.isfinite(h.reshape(-1)[:B * 512].float()).all())
 
 
 @pytest.mark.parametrize("backend", _params([()]))
@@ -699,15 +747,33 @@ def test_rejects_ln_mix(backend, be):
     outs = [_nan_like(be, B, 8200) for _ in range(7)]
     T = [I, I, I, VP, VP, VP, F32, VP, VP, VP]
 
-    def go(C=64, M=2):
-        x, lw, lb, prev = rnd(be, g, B, C), rnd(be, g, C), rnd(be, g, C), rnd(be, g, B, C)
-        keep = prev.clone()
-        rc = rc_of(be, "vrwkv_decode_ln_mix_bf16", T, B, C, M, P(x), P(lw), P(lb), EPS_LN, P(prev), arr([rnd(be, g, C) for _ in range(7)]), arr(outs))
-        assert rc == 0 or torch.equal(bits(prev), bits(keep)), "a rejected call replaced the carried row"
+    def go(B=B, C=64, M=2, null=(), off=(), mu_at=None, out_at=None):
+        Ct = max(C, 8)
+        t = dict(x=rnd(be, g, 2 + 1, Ct), ln_w=rnd(be, g, Ct + 8), ln_b=rnd(be, g, Ct + 8), x_prev=rnd(be, g, 2 + 1, Ct))
+        keep = t["x_prev"].clone()
+        ad = {k: VP(0 if k in null else v.data_ptr() + (2 if k in off else 0)) for k, v in t.items()}
+        mus, os_ = [rnd(be, g, Ct + 8).data_ptr() for _ in range(7)], [o.data_ptr() for o in outs]
+        if mu_at is not None:
+            mus[mu_at[0]] = mus[mu_at[0]] + 2 if mu_at[1] else 0
+        if out_at is not None:
+            os_[out_at[0]] = os_[out_at[0]] + 2 if out_at[1] else 0
+        rc = rc_of(be, "vrwkv_decode_ln_mix_bf16", T, B, C, M, ad["x"], ad["ln_w"], ad["ln_b"], EPS_LN, ad["x_prev"],
+                   None if "mu" in null else arr(mus), None if "out" in null else arr(os_))
+        assert rc == 0 or torch.equal(bits(t["x_prev"]), bits(keep)), "a rejected call replaced the carried row"
         return rc
 
-    assert go(C=12) == ESHAPE and go(C=8200) == ESHAPE and go(M=7) == EINVAL
+    assert go(C=12) == ESHAPE and go(C=8200) == ESHAPE and go(C=0) == ESHAPE
+    assert go(M=7) == EINVAL and go(M=0) == EINVAL and go(B=0) == EINVAL
+    for name in ("x", "ln_w", "ln_b", "x_prev", "mu", "out"):
+        assert go(null=(name,)) == EINVAL, name
+    assert go(mu_at=(1, 0)) == EINVAL and go(out_at=(0, 0)) == EINVAL
+    for name in ("x", "ln_w", "ln_b", "x_prev"):
+        assert go(off=(name,)) == EALIGN, name
+    assert go(mu_at=(0, 2)) == EALIGN and go(out_at=(1, 2)) == EALIGN
+    # two faults
+    assert go(M=7, C=12) == EINVAL and go(C=12, off=("x",)) == ESHAPE and go(mu_at=(1, 0), off=("x",)) == EINVAL
     _untouched(*outs)
+    assert go(mu_at=(2, 0)) == 0 and go(out_at=(2, 2)) == 0                 # past M: not looked at
     assert go() == 0
 
 
@@ -715,17 +781,105 @@ def test_rejects_ln_mix(backend, be):
 def test_rejects_tmix_head(backend, be):
     g = be.gen(6)
     B, H = 2, 2
-    p = head_inputs(be, g, B, H, HEAD_D["D32"], later=True)
-    out, src, dst = _nan_like(be, B, H * 64), rnd(be, g, B, H * 64), _nan_like(be, B, H * 64)
-    state = torch.full((B * H * 4096 + 4,), float("nan"), dtype=torch.float32, device=be.dev)
+    C = H * 64
+    p = head_inputs(be, g, B + 1, H, HEAD_D["D32"], later=True)
+    names = ("r", "k", "v", "vf", "w0", "a0", "v0", "k_k", "k_a", "r_k", "ln_w", "ln_b")
+    t = {n: _pad(p[n]) for n in names}
+    t["hid"], t["W2t"] = [_pad(h) for h in p["hid"]], [_pad(w) for w in p["W2t"]]
+    t["src"], t["out"], t["dst"] = rnd(be, g, (B + 1) * C + 8), _nan_like(be, (B + 1) * C + 8), _nan_like(be, (B + 1) * C + 8)
+    t["state"] = torch.full(((B + 1) * H * 4096 + 4,), float("nan"), dtype=torch.float32, device=be.dev)
 
-    def go(D=p["D"], src=None, dst=None, v0=p["v0"], st=state.data_ptr()):
-        return rc_of(be, "vrwkv_decode_tmix_head_bf16", HEAD_ARGT, B, H, P(p["r"]), P(p["k"]), P(p["v"]), P(p["vf"]), arr(p["hid"]), arr(p["W2t"]),
-                     ints(list(D)), P(p["w0"]), P(p["a0"]), P(v0), P(p["k_k"]), P(p["k_a"]), P(p["r_k"]), P(p["ln_w"]), P(p["ln_b"]), EPS_GN,
-                     VP(st), P(out), P(src), P(dst))
+    def go(B=B, H=H, D=p["D"], null=(), off=(), carry=False, hid_at=None, w2_at=None, t=t):
+        def ad(n):
+            return VP(0 if n in null else t[n].data_ptr() + ((4 if n == "state" else 2) if n in off else 0))
+        hid, w2 = [h.data_ptr() for h in t["hid"]], [w.data_ptr() for w in t["W2t"]]
+        if hid_at is not None:
+            hid[hid_at[0]] = hid[hid_at[0]] + 2 if hid_at[1] else 0
+        if w2_at is not None:
+            w2[w2_at[0]] = w2[w2_at[0]] + 2 if w2_at[1] else 0
+        src = ad("src") if carry in (True, "src") else None
+        dst = ad("dst") if carry in (True, "dst") else None
+        return rc_of(be, "vrwkv_decode_tmix_head_bf16", HEAD_ARGT, B, H, ad("r"), ad("k"), ad("v"), ad("vf"), None if "hid" in null else arr(hid),
+                     None if "W2t" in null else arr(w2), None if "D" in null else ints(list(D)), ad("w0"), ad("a0"), ad("v0"), ad("k_k"), ad("k_a"),
+                     ad("r_k"), ad("ln_w"), ad("ln_b"), EPS_GN, ad("state"), ad("out"), src, dst)
 
-    assert go(D=(48, 32, 32, 32)) == ESHAPE
-    assert go(src=src) == EINVAL and go(dst=dst) == EINVAL
-    assert go(v0=None) == EINVAL
-    assert go(st=state.data_ptr() + 4) == EALIGN
-    _untouched(out, dst, state)
+    assert go(B=0) == EINVAL and go(H=0) == EINVAL
+    assert go(D=(48, 32, 32, 32)) == ESHAPE and go(D=(32, 32, 0, 32)) == ESHAPE and go(D=(32, 32, 32, 16)) == ESHAPE
+    assert go(carry="src") == EINVAL and go(carry="dst") == EINVAL
+    for name in ("r", "k", "v", "hid", "W2t", "D", "w0", "a0", "k_k", "k_a", "r_k", "ln_w", "ln_b", "state", "out"):
+        assert go(null=(name,)) == EINVAL, name
+    assert go(null=("v0",)) == EINVAL                                      # a value residual (v_first) needs v0
+    assert go(hid_at=(1, 0)) == EINVAL and go(w2_at=(3, 0)) == EINVAL
+    assert go(off=("state",)) == EALIGN and go(hid_at=(0, 2)) == EALIGN and go(w2_at=(2, 2)) == EALIGN
+    # two faults: the state's alignment comes before the LoRA loop, which takes NULL, width, alignment factor by factor
+    assert go(D=(48, 32, 32, 32), off=("state",)) == EALIGN and go(null=("r",), off=("state",)) == EINVAL and go(B=0, carry="src") == EINVAL
+    assert go(D=(48, 32, 32, 32), hid_at=(1, 0)) == ESHAPE and go(D=(48, 32, 32, 32), hid_at=(0, 0)) == EINVAL
+    assert go(D=(32, 48, 32, 32), hid_at=(0, 2)) == EALIGN
+    _untouched(t["out"], t["dst"], t["state"])
+    # what the entry reads and writes by element is not checked for alignment: all of it 2 bytes off in one accepted call; layer 0
+    # (v_first NULL) takes neither v0 nor the fourth LoRA pair
+    t2 = dict(t, out=_nan_like(be, (B + 1) * C + 8), dst=_nan_like(be, (B + 1) * C + 8), state=torch.zeros_like(t["state"]))
+    assert go(off=names + ("out", "src", "dst"), carry=True, t=t2) == 0
+    assert bool(torch.isfinite(t2["out"][1:1 + B * C].float()).all()) and bool(torch.isnan(t2["out"][1 + B * C:].float()).all())
+    assert torch.equal(bits(t2["dst"][1:1 + B * C]), bits(t2["src"][1:1 + B * C])) and bool(torch.isnan(t2["dst"][1 + B * C:].float()).all())
+    t2["state"].zero_()
+    assert go(null=("vf", "v0"), hid_at=(3, 0), w2_at=(3, 0), D=(32, 32, 32, 0), t=t2) == 0
+    _untouched(t["out"], t["dst"], t["state"])
+
+
+@pytest.mark.parametrize("backend", _params([()]))
+def test_rejects_wkv7_step(backend, be):
+    g = be.gen(7)
+    names = ("w", "q", "k", "v", "z", "a")
+    t = {n: rnd(be, g, 2 * 64 + 8, scale=0.1) for n in names}
+    t["y"] = _nan_like(be, 2 * 64 + 8)
+    t["state"] = torch.full((2 * 4096 + 4,), float("nan"), dtype=torch.float32, device=be.dev)
+
+    def go(B=1, H=1, null=(), off=(), t=t):
+        ad = [VP(0 if n in null else t[n].data_ptr() + ((4 if n == "state" else 2) if n in off else 0)) for n in names + ("state", "y")]
+        return rc_of(be, "vrwkv_wkv7_step_bf16", [I, I] + [VP] * 8, B, H, *ad)
+
+    assert go(B=0) == EINVAL and go(H=0) == EINVAL                          # no cap on either: one workgroup per (b, h)
+    for name in names + ("state", "y"):
+        assert go(null=(name,)) == EINVAL, name
+    assert go(off=("state",)) == EALIGN
+    assert go(null=("w",), off=("state",)) == EINVAL and go(B=0, off=("state",)) == EINVAL          # two faults
+    _untouched(t["y"], t["state"])
+    t2 = dict(t, y=_nan_like(be, 2 * 64 + 8), state=torch.zeros_like(t["state"]))
+    assert go(off=names + ("y",), t=t2) == 0                                # the vectors are read and written by element: not checked
+    assert bool(torch.isfinite(t2["y"][1:65].float()).all()) and bool(torch.isnan(t2["y"][65:].float()).all())
+    assert go(B=2, t=t2) == 0
+    _untouched(t["y"], t["state"])
+
+
+# ------------------------------------------------------------------------------------------------ entries that forward to one launcher
+@pytest.mark.parametrize("backend", _params([()]))
+def test_gemv_entries_agree(backend, be):
+    """vrwkv_gemv_multi_bf16, the copy entry with copy_elems = 0 and the gated entry with a gate of ones and no copy: a product times 1.0
+    is exact, so the three give the same bits.  One launch of three jobs on the three K paths at their edges: K = 64 (short rows), 512
+    (exactly GV_LONG_KCHUNKS chunks), 2080 (the smallest K > 2048 with K % 32 == 0); N = 9 leaves the last workgroup partial (32 and 8
+    rows per workgroup), N = 3 the split-K tail (2 rows)."""
+    B = 2
+    jobs = gemv_jobs(be, be.gen(11), B, [(9, 64), (9, 512), (3, 2080)], rot=3)       # activations 3, 0, 1; residuals on the first and the last
+    plain = run_gemv(be, B, jobs)
+    copy0 = run_gemv(be, B, jobs, copy=(None, None, 0))
+    gated = [nan_rows(be, B, j["W"].shape[0]) for j in jobs]
+    ones = [torch.ones(B, j["W"].shape[0], dtype=torch.bfloat16, device=be.dev) for j in jobs]
+    be.call("vrwkv_gemv_gated_copy_bf16", [I, I] + [VP] * 10 + [L], len(jobs), B, arr([j["W"] for j in jobs]), arr([j["x"] for j in jobs]),
+            arr([j["res"] for j in jobs]), arr(ones), arr(gated), ints([j["W"].shape[0] for j in jobs]), ints([j["W"].shape[1] for j in jobs]),
+            ints([j["act"] for j in jobs]), None, None, 0)
+    written({f"y{j}": y for j, y in enumerate(gated)}, None, 0)
+    assert any(j["res"] is not None for j in jobs) and any(j["res"] is None for j in jobs)
+    same_bits(dict(enumerate(copy0)), dict(enumerate(plain)))
+    same_bits(dict(enumerate(gated)), dict(enumerate(plain)))
+    check_gemv(be, [(B, jobs, plain)], "gemv/entries")
+
+
+def test_fold_cases_reach_every_instantiation():
+    """gemv_ln_kernel<CH, BB>: CH = 2 chunks per thread for K > 2048, BB = 1, 2 or 4 batch rows compiled in (3 rides on 4).  test_fold's
+    K x B grid reaches all six, and B = 3 on both sides of 2048."""
+    inst = lambda K, B: (2 if K > 2048 else 1, 1 if B == 1 else 2 if B == 2 else 4)
+    grid = [(K, B) for K, _ in FOLD_K for B in (1, 2, 3, 4)]
+    assert {inst(K, B) for K, B in grid} == {(ch, bb) for ch in (1, 2) for bb in (1, 2, 4)}
+    assert {inst(K, 3) for K, B in grid if B == 3} == {(1, 4), (2, 4)}
+    assert all(512 <= K <= 4096 and K % 8 == 0 for K, _ in grid)

@@ -297,7 +297,7 @@ def test_gemv_copy_side_job_and_head_carry():
     g = torch.Generator(device="cuda").manual_seed(5)
     rn = lambda *s: (torch.randn(*s, device="cuda", generator=g) * 0.3).bfloat16()
     W, x, src, dst = rn(100, 1024), rn(2, 1024), rn(2, 2048), rn(2, 2048)
-    (y,) = decode.gemv_multi_copy([(W, x, None, decode.ACT_NONE)], 2, torch.device("cuda"), src, dst)
+    (y,) = decode.gemv_multi([(W, x, None, decode.ACT_NONE)], 2, torch.device("cuda"), copy=(src, dst))
     assert torch.equal(dst, src)
     assert rel_rms(y.float(), x.float() @ W.float().t()) < 5e-3
     m = _lm(fused=True).blocks[1].att

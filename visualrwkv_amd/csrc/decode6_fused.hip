@@ -14,27 +14,18 @@
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
+#include "decode_common.h"
 #include "host_checks.h"
-typedef uint32_t vrwkv_u4 __attribute__((ext_vector_type(4)));
 
 namespace {
+
+using namespace decode;
 
 constexpr int D6_MAX_B = 4;
 constexpr int D6_MAX_C = 8192;
 constexpr int D6_THREADS = 256;
 constexpr int D6_SLOTS = D6_THREADS / 8;       // 32 LoRA rows in flight per workgroup: thread (chunk cl, slot ds)
 constexpr int D6_PAD = 68;                     // row stride of the partial sums: the slots of a wave start 4 banks apart, rows stay 16-byte aligned
-
-DEVFN float rb(float x) { return __uint_as_float(f32_to_bf16_bits(x) << 16); }     // round to bf16, keep as fp32
-
-DEVFN void unpack8(const vrwkv_u4& u, float* f) {
-    f[0] = bf16_lo(u.x); f[1] = bf16_hi(u.x); f[2] = bf16_lo(u.y); f[3] = bf16_hi(u.y);
-    f[4] = bf16_lo(u.z); f[5] = bf16_hi(u.z); f[6] = bf16_lo(u.w); f[7] = bf16_hi(u.w);
-}
-DEVFN vrwkv_u4 pack8(const float* f) {
-    return vrwkv_u4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
-}
-DEVFN vrwkv_u4 ld16(const uint16_t* p) { return *reinterpret_cast<const vrwkv_u4*>(p); }
 
 struct DdArgs {
     const uint16_t *h, *hid, *w2;              // (B,C), (B,5 D), (5,D,C)
@@ -133,9 +124,9 @@ __global__ __launch_bounds__(D6_THREADS) void tmix6_head_kernel(Head6Args p) {
     const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
     const size_t cb = (size_t)b * p.C + h * 64;          // this head's 64 channels of batch row b
     float* sp = p.state + (size_t)blockIdx.x * 4096;
-    float4 st[4];
+    float4 st[STATE_VECS / D6_THREADS];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) st[i] = reinterpret_cast<const float4*>(sp)[tid + i * D6_THREADS];
+    for (int i = 0; i < STATE_VECS / D6_THREADS; ++i) st[i] = reinterpret_cast<const float4*>(sp)[tid + i * D6_THREADS];
     vrwkv_u4 w[R];
     float hv[R];
 #pragma unroll
@@ -164,10 +155,7 @@ __global__ __launch_bounds__(D6_THREADS) void tmix6_head_kernel(Head6Args p) {
         dst[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = tid + i * D6_THREADS, r = e >> 4, cc = (e & 15) * 4;
-        S[r][cc] = st[i].x; S[r][cc + 1] = st[i].y; S[r][cc + 2] = st[i].z; S[r][cc + 3] = st[i].w;
-    }
+    for (int i = 0; i < STATE_VECS / D6_THREADS; ++i) state_put(S, tid + i * D6_THREADS, st[i]);
     __syncthreads();
     if (qd == 0) {
         float lo = 0.f;
@@ -190,19 +178,15 @@ __global__ __launch_bounds__(D6_THREADS) void tmix6_head_kernel(Head6Args p) {
     __syncthreads();
     if (qd == 0) {
         y = rb((ypart[0][c] + ypart[1][c]) + (ypart[2][c] + ypart[3][c]));
-        const float mean = group_sum<6>(y) * (1.f / 64.f);
-        const float dlt = y - mean;
-        const float rstd = fast_rsqrt(group_sum<6>(dlt * dlt) * (1.f / 64.f) + p.eps);
+        float rstd;
+        const float dlt = groupnorm64(y, p.eps, rstd);
         const float gn = rb(dlt * rstd * vec[6][c] + vec[7][c]);
         const float g = vec[3][c];
         const float sg = rb(g / (1.f + fast_exp(-g)));
         p.out[cb + c] = (uint16_t)f32_to_bf16_bits(gn * sg);
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = tid + i * D6_THREADS, r = e >> 4, cc = (e & 15) * 4;
-        reinterpret_cast<float4*>(sp)[e] = make_float4(S[r][cc], S[r][cc + 1], S[r][cc + 2], S[r][cc + 3]);
-    }
+    for (int i = 0; i < STATE_VECS / D6_THREADS; ++i) reinterpret_cast<float4*>(sp)[tid + i * D6_THREADS] = state_get(S, tid + i * D6_THREADS);
 }
 
 inline bool bad_width(int C) { return C <= 0 || C % 64 != 0 || C > D6_MAX_C; }
@@ -215,14 +199,13 @@ extern "C" int vrwkv_decode6_ddlerp_bf16(int B, int C, int D, const void* h, voi
     if (bad_width(C) || (D != 32 && D != 64)) return VRWKV_ESHAPE;
     DdArgs a{};
     a.h = (const uint16_t*)h; a.x_prev = (uint16_t*)x_prev; a.hid = (const uint16_t*)hid; a.w2 = (const uint16_t*)w2; a.C = C;
-    uintptr_t al = reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(x_prev) | reinterpret_cast<uintptr_t>(hid) |
-                   reinterpret_cast<uintptr_t>(w2);
+    bool off = hostchk::any_misaligned(h, x_prev, hid, w2);
     for (int j = 0; j < 5; ++j) {
-        if (!maa[j] || !out[j]) return VRWKV_EINVAL;
+        if (hostchk::any_null(maa[j], out[j])) return VRWKV_EINVAL;
         a.maa[j] = (const uint16_t*)maa[j]; a.out[j] = (uint16_t*)out[j];
-        al |= reinterpret_cast<uintptr_t>(maa[j]) | reinterpret_cast<uintptr_t>(out[j]);
+        off |= hostchk::any_misaligned(maa[j], out[j]);
     }
-    if (al & 15u) return VRWKV_EALIGN;
+    if (off) return VRWKV_EALIGN;          // after every NULL of the arrays: EINVAL comes first
     const dim3 grid((unsigned)(C / 64), (unsigned)B), block(D6_THREADS);
     if (D == 32) hipLaunchKernelGGL(ddlerp_kernel<1>, grid, block, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(ddlerp_kernel<2>, grid, block, 0, (hipStream_t)stream, a);
@@ -234,10 +217,7 @@ extern "C" int vrwkv_decode6_tmix_head_bf16(int B, int H, int d_decay, const voi
                                             const void* ln_b, float eps, float* state, void* out, void* stream) {
     if (B <= 0 || B > D6_MAX_B || H <= 0 || hostchk::any_null(r, k, v, g, hid, w2, time_decay, u, ln_w, ln_b, state, out)) return VRWKV_EINVAL;
     if (bad_width(H * 64) || (d_decay != 64 && d_decay != 128)) return VRWKV_ESHAPE;
-    if ((reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(g) |
-         reinterpret_cast<uintptr_t>(hid) | reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(time_decay) | reinterpret_cast<uintptr_t>(u) |
-         reinterpret_cast<uintptr_t>(ln_w) | reinterpret_cast<uintptr_t>(ln_b) | reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(out)) & 15u)
-        return VRWKV_EALIGN;
+    if (hostchk::any_misaligned(r, k, v, g, hid, w2, time_decay, u, ln_w, ln_b, state, out)) return VRWKV_EALIGN;
     Head6Args p{};
     p.H = H; p.C = H * 64; p.Dd = d_decay;
     p.r = (const uint16_t*)r; p.k = (const uint16_t*)k; p.v = (const uint16_t*)v; p.g = (const uint16_t*)g;

@@ -16,33 +16,18 @@
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
-// 16-byte register pieces as the compiler's NATIVE vector type: private arrays of HIP's uint4 (a struct of unions) are not
-// promoted to registers and ended up in scratch memory (32 B/lane in the LayerNorm prologues of this file).
-typedef uint32_t vrwkv_u4 __attribute__((ext_vector_type(4)));
-#define uint4 vrwkv_u4
-#define make_uint4(a_, b_, c_, d_) (vrwkv_u4{(uint32_t)(a_), (uint32_t)(b_), (uint32_t)(c_), (uint32_t)(d_)})
+#include "decode_common.h"
+#include "host_checks.h"
 
 namespace {
+
+using namespace decode;
 
 constexpr int LM_MAXM = 6;
 constexpr int LM_THREADS = 256;
 constexpr int LM_MAXCH = 4;                  // 8-channel chunks per thread: C <= 8192
 
-DEVFN float rb(float x) { return __uint_as_float(f32_to_bf16_bits(x) << 16); }     // round to bf16, keep as fp32
 DEVFN float sigmoidf_(float x) { return 1.f / (1.f + fast_exp(-x)); }
-
-struct V8 { float f[8]; };
-DEVFN V8 ld8f(const uint16_t* p) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    V8 r;
-    r.f[0] = bf16_lo(u.x); r.f[1] = bf16_hi(u.x); r.f[2] = bf16_lo(u.y); r.f[3] = bf16_hi(u.y);
-    r.f[4] = bf16_lo(u.z); r.f[5] = bf16_hi(u.z); r.f[6] = bf16_lo(u.w); r.f[7] = bf16_hi(u.w);
-    return r;
-}
-DEVFN void st8f(uint16_t* p, const V8& v) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(pack_bf16x2(v.f[0], v.f[1]), pack_bf16x2(v.f[2], v.f[3]),
-                                              pack_bf16x2(v.f[4], v.f[5]), pack_bf16x2(v.f[6], v.f[7]));
-}
 
 // sum over the workgroup (4 waves); every thread gets the result
 DEVFN float wg_sum(float v, float* red) {
@@ -62,12 +47,10 @@ struct LnMixArgs {
     float eps;
 };
 
-DEVFN V8 unpack(const uint4& u) {
-    V8 r;
-    r.f[0] = bf16_lo(u.x); r.f[1] = bf16_hi(u.x); r.f[2] = bf16_lo(u.y); r.f[3] = bf16_hi(u.y);
-    r.f[4] = bf16_lo(u.z); r.f[5] = bf16_hi(u.z); r.f[6] = bf16_lo(u.w); r.f[7] = bf16_hi(u.w);
-    return r;
-}
+// The row kernel below holds its chunks by value: the pointer spelling of unpack8 / pack8 reorders its instructions (measured +1.3 % at C = 8192).
+struct V8 { float f[8]; };
+DEVFN V8 unpack(const vrwkv_u4& u) { V8 r; unpack8(u, r.f); return r; }
+DEVFN void st8f(uint16_t* p, const V8& v) { *reinterpret_cast<vrwkv_u4*>(p) = pack8(v.f); }
 
 // One workgroup per row.  Everything the row needs (x, LayerNorm parameters, the carried row, the lerp coefficients)
 // is loaded before the first reduction: one memory round trip per launch.
@@ -75,18 +58,18 @@ __global__ __launch_bounds__(LM_THREADS) void ln_mix_prev_kernel(LnMixArgs a) {
     __shared__ float red[4];
     const int C = a.C, nch = C / 8;
     const size_t row = (size_t)blockIdx.x * C;
-    const uint4 zero = make_uint4(0, 0, 0, 0);
-    uint4 xr[LM_MAXCH], lwr[LM_MAXCH], lbr[LM_MAXCH], xpr[LM_MAXCH], mur[LM_MAXCH][LM_MAXM];
+    const vrwkv_u4 zero = vrwkv_u4{0, 0, 0, 0};
+    vrwkv_u4 xr[LM_MAXCH], lwr[LM_MAXCH], lbr[LM_MAXCH], xpr[LM_MAXCH], mur[LM_MAXCH][LM_MAXM];
 #pragma unroll
     for (int i = 0; i < LM_MAXCH; ++i) {
         const int ch = threadIdx.x + i * LM_THREADS;
         const bool live = ch < nch;
-        xr[i] = live ? *reinterpret_cast<const uint4*>(a.x + row + ch * 8) : zero;
-        lwr[i] = live ? *reinterpret_cast<const uint4*>(a.ln_w + ch * 8) : zero;
-        lbr[i] = live ? *reinterpret_cast<const uint4*>(a.ln_b + ch * 8) : zero;
-        xpr[i] = live ? *reinterpret_cast<const uint4*>(a.x_prev + row + ch * 8) : zero;
+        xr[i] = live ? ld16(a.x + row + ch * 8) : zero;
+        lwr[i] = live ? ld16(a.ln_w + ch * 8) : zero;
+        lbr[i] = live ? ld16(a.ln_b + ch * 8) : zero;
+        xpr[i] = live ? ld16(a.x_prev + row + ch * 8) : zero;
 #pragma unroll
-        for (int j = 0; j < LM_MAXM; ++j) mur[i][j] = (live && j < a.M) ? *reinterpret_cast<const uint4*>(a.mu[j] + ch * 8) : zero;
+        for (int j = 0; j < LM_MAXM; ++j) mur[i][j] = (live && j < a.M) ? ld16(a.mu[j] + ch * 8) : zero;
     }
     float s = 0.f;
 #pragma unroll
@@ -149,7 +132,7 @@ struct HeadArgs {
     uint16_t* carry_dst;
 };
 
-DEVFN float dot8(const uint4& a, const uint4& b) {
+DEVFN float dot8(const vrwkv_u4& a, const vrwkv_u4& b) {
     return bf16_lo(a.x) * bf16_lo(b.x) + bf16_hi(a.x) * bf16_hi(b.x) + bf16_lo(a.y) * bf16_lo(b.y) + bf16_hi(a.y) * bf16_hi(b.y)
          + bf16_lo(a.z) * bf16_lo(b.z) + bf16_hi(a.z) * bf16_hi(b.z) + bf16_lo(a.w) * bf16_lo(b.w) + bf16_hi(a.w) * bf16_hi(b.w);
 }
@@ -165,9 +148,9 @@ __global__ __launch_bounds__(TH_THREADS) void tmix_head_kernel(HeadArgs p) {
     const size_t cb = (size_t)b * p.C + h * 64;          // this head's 64 channels of batch row b
     const int hc = h * 64 + c;
     float* sp = p.state + (size_t)blockIdx.x * 4096;
-    float4 st[4];
+    float4 st[STATE_VECS / TH_THREADS];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) st[i] = reinterpret_cast<const float4*>(sp)[tid + i * TH_THREADS];
+    for (int i = 0; i < STATE_VECS / TH_THREADS; ++i) st[i] = reinterpret_cast<const float4*>(sp)[tid + i * TH_THREADS];
     if (p.carry_src && qd == 1) p.carry_dst[cb + c] = p.carry_src[cb + c];
     const bool vres = p.v_first != nullptr;
     const int nk = vres ? 4 : 3;
@@ -183,18 +166,15 @@ __global__ __launch_bounds__(TH_THREADS) void tmix_head_kernel(HeadArgs p) {
         float acc = 0.f;
         if (i < nk) {
             const int D = p.D[i], Dq = D / 4;
-            const uint4* W = reinterpret_cast<const uint4*>(p.W2t[i] + (size_t)hc * D + qd * Dq);
-            const uint4* hv = reinterpret_cast<const uint4*>(p.hid[i] + (size_t)b * D + qd * Dq);
+            const vrwkv_u4* W = reinterpret_cast<const vrwkv_u4*>(p.W2t[i] + (size_t)hc * D + qd * Dq);
+            const vrwkv_u4* hv = reinterpret_cast<const vrwkv_u4*>(p.hid[i] + (size_t)b * D + qd * Dq);
 #pragma unroll 4
             for (int ch = 0; ch < Dq / 8; ++ch) acc += dot8(W[ch], hv[ch]);
         }
         part[i][qd][c] = acc;
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = tid + i * TH_THREADS, r = e >> 4, cc = (e & 15) * 4;
-        S[r][cc] = st[i].x; S[r][cc + 1] = st[i].y; S[r][cc + 2] = st[i].z; S[r][cc + 3] = st[i].w;
-    }
+    for (int i = 0; i < STATE_VECS / TH_THREADS; ++i) state_put(S, tid + i * TH_THREADS, st[i]);
     __syncthreads();
     float gate = 0.f, k2 = 0.f, v2 = 0.f;
     if (qd == 0) {
@@ -241,39 +221,33 @@ __global__ __launch_bounds__(TH_THREADS) void tmix_head_kernel(HeadArgs p) {
     if (qd == 0) {
         y = rb(part[1][0][c] + part[1][1][c] + part[1][2][c] + part[1][3][c]);
         // GroupNorm over the head + bonus + gate (post_fwd_kernel)
-        const float mean = group_sum<6>(y) * (1.f / 64.f);
-        const float dlt = y - mean;
-        const float rstd = fast_rsqrt(group_sum<6>(dlt * dlt) * (1.f / 64.f) + p.eps);
+        float rstd;
+        const float dlt = groupnorm64(y, p.eps, rstd);
         const float sb = group_sum<6>(rr * k2 * r_k);
         p.out[cb + c] = (uint16_t)f32_to_bf16_bits((dlt * rstd * ln_w + ln_b + sb * v2) * gate);
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = tid + i * TH_THREADS, r = e >> 4, cc = (e & 15) * 4;
-        reinterpret_cast<float4*>(sp)[e] = make_float4(S[r][cc], S[r][cc + 1], S[r][cc + 2], S[r][cc + 3]);
-    }
+    for (int i = 0; i < STATE_VECS / TH_THREADS; ++i) reinterpret_cast<float4*>(sp)[tid + i * TH_THREADS] = state_get(S, tid + i * TH_THREADS);
 }
 
 }  // namespace
 
 extern "C" int vrwkv_decode_ln_mix_bf16(int B, int C, int M, const void* x, const void* ln_w, const void* ln_b, float eps,
                                         void* x_prev, const void* const* mu, void* const* out, void* stream) {
-    if (B <= 0 || M <= 0 || M > LM_MAXM || !x || !ln_w || !ln_b || !x_prev || !mu || !out) return VRWKV_EINVAL;
+    if (B <= 0 || M <= 0 || M > LM_MAXM || hostchk::any_null(x, ln_w, ln_b, x_prev, mu, out)) return VRWKV_EINVAL;
     if (C <= 0 || C % 8 != 0 || C > 8 * LM_THREADS * LM_MAXCH) return VRWKV_ESHAPE;
     LnMixArgs a{};
     a.x = (const uint16_t*)x; a.ln_w = (const uint16_t*)ln_w; a.ln_b = (const uint16_t*)ln_b; a.x_prev = (uint16_t*)x_prev;
     a.C = C; a.M = M; a.eps = eps;
-    uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ln_w) | reinterpret_cast<uintptr_t>(ln_b) |
-                   reinterpret_cast<uintptr_t>(x_prev);
+    bool off = hostchk::any_misaligned(x, ln_w, ln_b, x_prev);
     for (int j = 0; j < M; ++j) {
-        if (!mu[j] || !out[j]) return VRWKV_EINVAL;
+        if (hostchk::any_null(mu[j], out[j])) return VRWKV_EINVAL;
         a.mu[j] = (const uint16_t*)mu[j]; a.out[j] = (uint16_t*)out[j];
-        al |= reinterpret_cast<uintptr_t>(mu[j]) | reinterpret_cast<uintptr_t>(out[j]);
+        off |= hostchk::any_misaligned(mu[j], out[j]);
     }
-    if (al & 15u) return VRWKV_EALIGN;
+    if (off) return VRWKV_EALIGN;          // after every NULL of the arrays: EINVAL comes first
     hipLaunchKernelGGL(ln_mix_prev_kernel, dim3((unsigned)B), dim3(LM_THREADS), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return hostchk::finish_launch();
 }
 
 extern "C" int vrwkv_decode_tmix_head_bf16(int B, int H, const void* r, const void* k, const void* v, const void* v_first,
@@ -283,18 +257,17 @@ extern "C" int vrwkv_decode_tmix_head_bf16(int B, int H, const void* r, const vo
                                            float* state, void* out, const void* carry_src, void* carry_dst,
                                            void* stream) {
     if ((carry_src == nullptr) != (carry_dst == nullptr)) return VRWKV_EINVAL;
-    if (B <= 0 || H <= 0 || !r || !k || !v || !hid || !W2t || !D || !w0 || !a0 || !k_k || !k_a || !r_k || !ln_w || !ln_b ||
-        !state || !out) return VRWKV_EINVAL;
+    if (B <= 0 || H <= 0 || hostchk::any_null(r, k, v, hid, W2t, D, w0, a0, k_k, k_a, r_k, ln_w, ln_b, state, out)) return VRWKV_EINVAL;      // no cap on B
     if (v_first && !v0) return VRWKV_EINVAL;
-    if (reinterpret_cast<uintptr_t>(state) & 15u) return VRWKV_EALIGN;
+    if (hostchk::misaligned(state)) return VRWKV_EALIGN;          // with hid / W2t below the only 16-byte accesses: the rest is read by element
     HeadArgs p{};
     p.B = B; p.H = H; p.C = H * 64;
     p.r = (const uint16_t*)r; p.k = (const uint16_t*)k; p.v = (const uint16_t*)v; p.v_first = (const uint16_t*)v_first;
     const int nk = v_first ? 4 : 3;
     for (int i = 0; i < nk; ++i) {
-        if (!hid[i] || !W2t[i]) return VRWKV_EINVAL;
+        if (hostchk::any_null(hid[i], W2t[i])) return VRWKV_EINVAL;
         if (D[i] <= 0 || D[i] % 32 != 0) return VRWKV_ESHAPE;
-        if ((reinterpret_cast<uintptr_t>(hid[i]) | reinterpret_cast<uintptr_t>(W2t[i])) & 15u) return VRWKV_EALIGN;
+        if (hostchk::any_misaligned(hid[i], W2t[i])) return VRWKV_EALIGN;
         p.hid[i] = (const uint16_t*)hid[i]; p.W2t[i] = (const uint16_t*)W2t[i]; p.D[i] = D[i];
     }
     p.w0 = (const uint16_t*)w0; p.a0 = (const uint16_t*)a0; p.v0 = (const uint16_t*)v0; p.k_k = (const uint16_t*)k_k;
@@ -302,6 +275,5 @@ extern "C" int vrwkv_decode_tmix_head_bf16(int B, int H, const void* r, const vo
     p.eps = eps; p.state = state; p.out = (uint16_t*)out;
     p.carry_src = (const uint16_t*)carry_src; p.carry_dst = (uint16_t*)carry_dst;
     hipLaunchKernelGGL(tmix_head_kernel, dim3((unsigned)(B * H)), dim3(TH_THREADS), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return hostchk::finish_launch();
 }

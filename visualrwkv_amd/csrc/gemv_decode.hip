@@ -27,13 +27,12 @@
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
-// 16-byte register pieces as the compiler's NATIVE vector type: private arrays of HIP's uint4 (a struct of unions) are not
-// promoted to registers and ended up in scratch memory (32 B/lane in the LayerNorm prologues of this file).
-typedef uint32_t vrwkv_u4 __attribute__((ext_vector_type(4)));
-#define uint4 vrwkv_u4
-#define make_uint4(a_, b_, c_, d_) (vrwkv_u4{(uint32_t)(a_), (uint32_t)(b_), (uint32_t)(c_), (uint32_t)(d_)})
+#include "decode_common.h"
+#include "host_checks.h"
 
 namespace {
+
+using namespace decode;
 
 constexpr int GV_MAX_JOBS = 8;
 constexpr int GV_MAX_B = 4;
@@ -62,10 +61,8 @@ struct GemvArgs {
     GemvJob job[GV_MAX_JOBS];
     int n_jobs, B;
     LnFold ln;
-    const uint4* copy_src; uint4* copy_dst; long copy_vec;      // side job: 16-byte vectors copied by workgroup 0
+    const vrwkv_u4* copy_src; vrwkv_u4* copy_dst; long copy_vec;      // side job: 16-byte vectors copied by workgroup 0
 };
-
-DEVFN float rb(float x) { return __uint_as_float(f32_to_bf16_bits(x) << 16); }     // round to bf16, keep as fp32
 
 DEVFN float apply_act(float v, int act) {
     if (act == 1) return 1.f - 2.f / (1.f + fast_exp(2.f * v));          // tanh
@@ -83,14 +80,6 @@ DEVFN void emit(const GemvJob& job, int N, int b, int n, float v) {
     job.y[(size_t)b * N + n] = (uint16_t)f32_to_bf16_bits(v);
 }
 
-DEVFN void unpack8(const uint4& u, float* f) {
-    f[0] = bf16_lo(u.x); f[1] = bf16_hi(u.x); f[2] = bf16_lo(u.y); f[3] = bf16_hi(u.y);
-    f[4] = bf16_lo(u.z); f[5] = bf16_hi(u.z); f[6] = bf16_lo(u.w); f[7] = bf16_hi(u.w);
-}
-DEVFN uint4 pack8(const float* f) {
-    return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
-}
-
 constexpr int GV_R = GV_LONG_ROWS_PER_WG / 4, GV_U = 4;      // rows per wave, 16-byte loads per row and lane in flight
 
 // Rows longer than 2048 (the 4C -> C projection of the channel mix) are split over the workgroup's waves instead:
@@ -99,13 +88,13 @@ constexpr int GV_R = GV_LONG_ROWS_PER_WG / 4, GV_U = 4;      // rows per wave, 1
 __host__ __device__ inline bool split_k(int K) { return K > 2048 && K % 32 == 0; }
 __host__ __device__ inline int long_rows_per_wg(int K) { return split_k(K) ? GV_LONG_ROWS_PER_WG / 4 : GV_LONG_ROWS_PER_WG; }
 
-DEVFN void load_batch(const GemvJob& job, int row0, int c0, int kchunks, uint4 (&u)[GV_R][GV_U]) {
+DEVFN void load_batch(const GemvJob& job, int row0, int c0, int kchunks, vrwkv_u4 (&u)[GV_R][GV_U]) {
 #pragma unroll
     for (int q = 0; q < GV_U; ++q)
 #pragma unroll
         for (int r = 0; r < GV_R; ++r) {
             const int n = row0 + r, c = c0 + 64 * q;
-            u[r][q] = (n < job.N && c < kchunks) ? *reinterpret_cast<const uint4*>(job.W + (size_t)n * job.K + c * 8) : make_uint4(0, 0, 0, 0);
+            u[r][q] = (n < job.N && c < kchunks) ? ld16(job.W + (size_t)n * job.K + c * 8) : vrwkv_u4{0, 0, 0, 0};
         }
 }
 
@@ -113,7 +102,7 @@ DEVFN void load_batch(const GemvJob& job, int row0, int c0, int kchunks, uint4 (
 // `first` holds the weights of the first batch (c0 = lane), loaded by the caller before whatever it had to wait for.
 // The walk covers chunks [c_begin, kchunks); acc holds per-lane partial sums.
 template <int BB, typename F>
-DEVFN void long_rows_acc(const GemvJob& job, int B, int row0, int lane, int c_begin, int kchunks, uint4 (&first)[GV_R][GV_U],
+DEVFN void long_rows_acc(const GemvJob& job, int B, int row0, int lane, int c_begin, int kchunks, vrwkv_u4 (&first)[GV_R][GV_U],
                          float (&acc)[GV_R][BB], F&& input) {
     constexpr int R = GV_R, U = GV_U;
 #pragma unroll
@@ -121,7 +110,7 @@ DEVFN void long_rows_acc(const GemvJob& job, int B, int row0, int lane, int c_be
 #pragma unroll
         for (int b = 0; b < BB; ++b) acc[r][b] = 0.f;
     for (int c0 = c_begin + lane; c0 < kchunks; c0 += 64 * U) {
-        uint4 u[R][U];
+        vrwkv_u4 u[R][U];
         if (c0 == c_begin + lane) {
 #pragma unroll
             for (int q = 0; q < U; ++q)
@@ -154,7 +143,7 @@ DEVFN void long_rows_acc(const GemvJob& job, int B, int row0, int lane, int c_be
 }
 
 template <int BB, bool GATED = false, typename F>
-DEVFN void long_rows(const GemvJob& job, int B, int row0, int lane, uint4 (&first)[GV_R][GV_U], F&& input) {
+DEVFN void long_rows(const GemvJob& job, int B, int row0, int lane, vrwkv_u4 (&first)[GV_R][GV_U], F&& input) {
     constexpr int R = GV_R;
     const int N = job.N;
     float acc[R][BB];
@@ -191,11 +180,11 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_multi_kernel(GemvArgs a) {
     if (split_k(K)) {
         __shared__ float part[4][GV_R][GV_MAX_B];
         const int row0 = ((int)blockIdx.x - job.wg_begin) * GV_R, kq = kchunks / 4;
-        uint4 first[GV_R][GV_U];
+        vrwkv_u4 first[GV_R][GV_U];
         load_batch(job, row0, wave * kq + lane, (wave + 1) * kq, first);
         float acc[GV_R][GV_MAX_B];
         long_rows_acc<GV_MAX_B>(job, B, row0, lane, wave * kq, (wave + 1) * kq, first, acc, [&](int b, int c, float* xv) {
-            unpack8(*reinterpret_cast<const uint4*>(job.x + (size_t)b * K + c * 8), xv);
+            unpack8(ld16(job.x + (size_t)b * K + c * 8), xv);
         });
 #pragma unroll
         for (int r = 0; r < GV_R; ++r)
@@ -211,14 +200,14 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_multi_kernel(GemvArgs a) {
         }
     } else if (kchunks >= GV_LONG_KCHUNKS) {
         const int row0 = ((int)blockIdx.x - job.wg_begin) * GV_LONG_ROWS_PER_WG + wave * GV_R;
-        uint4 first[GV_R][GV_U];
+        vrwkv_u4 first[GV_R][GV_U];
         load_batch(job, row0, lane, kchunks, first);
         long_rows<GV_MAX_B, GATED>(job, B, row0, lane, first, [&](int b, int c, float* xv) {
-            unpack8(*reinterpret_cast<const uint4*>(job.x + (size_t)b * K + c * 8), xv);
+            unpack8(ld16(job.x + (size_t)b * K + c * 8), xv);
         });
     } else {
         // short rows (LoRA up-projections, K = 64..256): a group of G lanes per row, 64/G rows at a time
-        for (int i = threadIdx.x * 8; i < B * K; i += GV_THREADS * 8) unpack8(*reinterpret_cast<const uint4*>(job.x + i), xs + i);
+        for (int i = threadIdx.x * 8; i < B * K; i += GV_THREADS * 8) unpack8(ld16(job.x + i), xs + i);
         __syncthreads();
         const int row0 = ((int)blockIdx.x - job.wg_begin) * GV_ROWS_PER_WG + wave * (GV_ROWS_PER_WG / 4);   // 8 rows per wave
         int G = 32;
@@ -230,7 +219,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_multi_kernel(GemvArgs a) {
             float acc[GV_MAX_B] = {0.f, 0.f, 0.f, 0.f};
             for (int c = gl; c < kchunks; c += G) {
                 float wv[8];
-                unpack8(live ? *reinterpret_cast<const uint4*>(job.W + (size_t)n * K + c * 8) : make_uint4(0, 0, 0, 0), wv);
+                unpack8(live ? ld16(job.W + (size_t)n * K + c * 8) : vrwkv_u4{0, 0, 0, 0}, wv);
 #pragma unroll
                 for (int b = 0; b < GV_MAX_B; ++b) {
                     if (b < B) {
@@ -261,28 +250,28 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_multi_kernel(GemvArgs a) {
 // itself the row's outlier: 1 .. 5 % of h then differ from the correctly rounded value (tests/test_decode_shapes.py).
 template <int CH, int BB>      // chunks per thread (K <= 2048 CH), batch rows compiled in: registers follow the real shape
 __global__ __launch_bounds__(GV_THREADS) void gemv_ln_kernel(GemvArgs a) {
-    uint4* xin = reinterpret_cast<uint4*>(dyn_lds());                   // [B][K/8] packed bf16 inputs
+    vrwkv_u4* xin = reinterpret_cast<vrwkv_u4*>(dyn_lds());           // [B][K/8] packed bf16 inputs
     __shared__ float red[2][4][BB];                                     // [pass][wave][batch row]
     const GemvJob job = a.job[find_job(a)];
     const int K = job.K, B = a.B, kchunks = K / 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row0 = ((int)blockIdx.x - job.wg_begin) * GV_LONG_ROWS_PER_WG + wave * GV_R;
-    uint4 first[GV_R][GV_U];
+    vrwkv_u4 first[GV_R][GV_U];
     load_batch(job, row0, lane, kchunks, first);         // the weight stream starts before the prologue's round trip
-    const uint4 zero = make_uint4(0, 0, 0, 0);
-    uint4 xr[CH][BB], pr[CH][BB], lwr[CH], lbr[CH], mur[CH];
+    const vrwkv_u4 zero = vrwkv_u4{0, 0, 0, 0};
+    vrwkv_u4 xr[CH][BB], pr[CH][BB], lwr[CH], lbr[CH], mur[CH];
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
         const int ch = threadIdx.x + i * GV_THREADS;
         const bool live = ch < kchunks;
-        lwr[i] = live ? *reinterpret_cast<const uint4*>(a.ln.ln_w + ch * 8) : zero;
-        lbr[i] = live ? *reinterpret_cast<const uint4*>(a.ln.ln_b + ch * 8) : zero;
-        mur[i] = live ? *reinterpret_cast<const uint4*>(job.mu + ch * 8) : zero;
+        lwr[i] = live ? ld16(a.ln.ln_w + ch * 8) : zero;
+        lbr[i] = live ? ld16(a.ln.ln_b + ch * 8) : zero;
+        mur[i] = live ? ld16(job.mu + ch * 8) : zero;
 #pragma unroll
         for (int b = 0; b < BB; ++b) {
             const bool lb_ = live && b < B;
-            xr[i][b] = lb_ ? *reinterpret_cast<const uint4*>(job.x + (size_t)b * K + ch * 8) : zero;
-            pr[i][b] = lb_ ? *reinterpret_cast<const uint4*>(a.ln.x_prev + (size_t)b * K + ch * 8) : zero;
+            xr[i][b] = lb_ ? ld16(job.x + (size_t)b * K + ch * 8) : zero;
+            pr[i][b] = lb_ ? ld16(a.ln.x_prev + (size_t)b * K + ch * 8) : zero;
         }
     }
 #pragma unroll
@@ -340,7 +329,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_ln_kernel(GemvArgs a) {
                         xv[e] = fmaf(xp[e] - h[e], mu[e], h[e]);
                     }
                     xin[b * kchunks + ch] = pack8(xv);
-                    if (writes_h) *reinterpret_cast<uint4*>(a.ln.h_out + (size_t)b * K + ch * 8) = pack8(h);
+                    if (writes_h) *reinterpret_cast<vrwkv_u4*>(a.ln.h_out + (size_t)b * K + ch * 8) = pack8(h);
                 }
             }
         }
@@ -349,80 +338,99 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_ln_kernel(GemvArgs a) {
     long_rows<BB>(job, B, row0, lane, first, [&](int b, int c, float* xv) { unpack8(xin[b * kchunks + c], xv); });
 }
 
-int launch(int n_jobs, int B, const void* const* W, const void* const* x, const void* const* res, const void* const* mu,
-           void* const* y, const int* N, const int* K, const int* act, const LnFold* ln, const void* copy_src,
-           void* copy_dst, long copy_elems, void* stream, const void* const* gate = nullptr) {
-    if (n_jobs <= 0 || n_jobs > GV_MAX_JOBS || B <= 0 || B > GV_MAX_B || !W || !x || !y || !N || !K || !act) return VRWKV_EINVAL;
-    if (copy_elems < 0 || (copy_elems > 0 && (!copy_src || !copy_dst))) return VRWKV_EINVAL;
-    if (copy_elems % 8 != 0) return VRWKV_ESHAPE;
-    if ((reinterpret_cast<uintptr_t>(copy_src) | reinterpret_cast<uintptr_t>(copy_dst)) & 15u) return VRWKV_EALIGN;
+// What an entry adds to the plain batched GEMV, each part optional.
+struct Extras {
+    const LnFold* ln = nullptr;              // LayerNorm fold, with the jobs' lerp coefficients
+    const void* const* mu = nullptr;
+    const void* const* gate = nullptr;       // gated entry
+    const void* copy_src = nullptr;          // copy side job
+    void* copy_dst = nullptr;
+    long copy_elems = 0;
+};
+
+// The instantiation of the fold for a row of K (chunks per thread) and B batch rows (compiled in: 1, 2, or 4 for 3 and 4).
+using LnKernel = void (*)(GemvArgs);
+inline LnKernel ln_kernel(int K, int B) {
+    static constexpr LnKernel table[2][3] = {{gemv_ln_kernel<1, 1>, gemv_ln_kernel<1, 2>, gemv_ln_kernel<1, 4>},
+                                             {gemv_ln_kernel<2, 1>, gemv_ln_kernel<2, 2>, gemv_ln_kernel<2, 4>}};
+    return table[K > 8 * GV_THREADS][B == 1 ? 0 : B == 2 ? 1 : 2];
+}
+
+// The order of the checks is what a caller with two faults at once sees: counts and the arrays themselves, the copy side job, then job by job.
+// A NULL W[j] / x[j] / y[j] answers ESHAPE like the job's N and K.
+int launch(int n_jobs, int B, const void* const* W, const void* const* x, const void* const* res, void* const* y, const int* N, const int* K,
+           const int* act, const Extras& e, void* stream) {
+    using namespace hostchk;
+    const LnFold* ln = e.ln;
+    if (n_jobs <= 0 || n_jobs > GV_MAX_JOBS || B <= 0 || B > GV_MAX_B || any_null(W, x, y, N, K, act)) return VRWKV_EINVAL;
+    if (e.copy_elems < 0 || (e.copy_elems > 0 && any_null(e.copy_src, e.copy_dst))) return VRWKV_EINVAL;
+    if (e.copy_elems % 8 != 0) return VRWKV_ESHAPE;
+    if (any_misaligned(e.copy_src, e.copy_dst)) return VRWKV_EALIGN;
     GemvArgs a{};
     a.n_jobs = n_jobs; a.B = B;
-    a.copy_src = (const uint4*)copy_src; a.copy_dst = (uint4*)copy_dst; a.copy_vec = copy_elems / 8;
+    a.copy_src = (const vrwkv_u4*)e.copy_src; a.copy_dst = (vrwkv_u4*)e.copy_dst; a.copy_vec = e.copy_elems / 8;
     if (ln) a.ln = *ln;
     int wg = 0, kmax = 0;
     for (int j = 0; j < n_jobs; ++j) {
-        if (!W[j] || !x[j] || !y[j] || N[j] <= 0 || K[j] <= 0 || K[j] % 8 != 0) return VRWKV_ESHAPE;
-        if ((reinterpret_cast<uintptr_t>(W[j]) | reinterpret_cast<uintptr_t>(x[j])) & 15u) return VRWKV_EALIGN;
+        if (any_null(W[j], x[j], y[j]) || N[j] <= 0 || K[j] <= 0 || K[j] % 8 != 0) return VRWKV_ESHAPE;
+        if (any_misaligned(W[j], x[j])) return VRWKV_EALIGN;
         const bool long_rows = K[j] / 8 >= GV_LONG_KCHUNKS;
         if (ln) {
             if (!long_rows || K[j] > GV_LN_MAX_K || K[j] != K[0] || x[j] != x[0]) return VRWKV_ESHAPE;
-            if (!mu || !mu[j]) return VRWKV_EINVAL;
-            if (reinterpret_cast<uintptr_t>(mu[j]) & 15u) return VRWKV_EALIGN;
+            if (!e.mu || !e.mu[j]) return VRWKV_EINVAL;
+            if (misaligned(e.mu[j])) return VRWKV_EALIGN;
         }
-        if (gate && !gate[j]) return VRWKV_EINVAL;
+        if (e.gate && !e.gate[j]) return VRWKV_EINVAL;
         a.job[j] = GemvJob{(const uint16_t*)W[j], (const uint16_t*)x[j], res ? (const uint16_t*)res[j] : nullptr,
-                           ln ? (const uint16_t*)mu[j] : nullptr, gate ? (const uint16_t*)gate[j] : nullptr, (uint16_t*)y[j], N[j], K[j],
+                           ln ? (const uint16_t*)e.mu[j] : nullptr, e.gate ? (const uint16_t*)e.gate[j] : nullptr, (uint16_t*)y[j], N[j], K[j],
                            act[j], wg};
         const int rows = ln ? GV_LONG_ROWS_PER_WG : long_rows ? long_rows_per_wg(K[j]) : GV_ROWS_PER_WG;
         wg += (N[j] + rows - 1) / rows;
         if (!long_rows) kmax = K[j] > kmax ? K[j] : kmax;
     }
-    const size_t lds = (size_t)B * kmax * sizeof(float);
-    if (ln) {
-        const dim3 g((unsigned)wg), t(GV_THREADS);
-        const size_t l = (size_t)B * K[0] * 2;
-        const hipStream_t st = (hipStream_t)stream;
-        const bool wide = K[0] > 8 * GV_THREADS;             // two chunks per thread
-        if (B == 1) { if (wide) hipLaunchKernelGGL((gemv_ln_kernel<2, 1>), g, t, l, st, a); else hipLaunchKernelGGL((gemv_ln_kernel<1, 1>), g, t, l, st, a); }
-        else if (B == 2) { if (wide) hipLaunchKernelGGL((gemv_ln_kernel<2, 2>), g, t, l, st, a); else hipLaunchKernelGGL((gemv_ln_kernel<1, 2>), g, t, l, st, a); }
-        else { if (wide) hipLaunchKernelGGL((gemv_ln_kernel<2, 4>), g, t, l, st, a); else hipLaunchKernelGGL((gemv_ln_kernel<1, 4>), g, t, l, st, a); }
-    }
-    else if (gate) hipLaunchKernelGGL(gemv_multi_kernel<true>, dim3((unsigned)wg), dim3(GV_THREADS), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(gemv_multi_kernel<false>, dim3((unsigned)wg), dim3(GV_THREADS), lds, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    const dim3 grid((unsigned)wg), block(GV_THREADS);
+    const size_t lds = (size_t)B * kmax * sizeof(float);         // short-row jobs: x as fp32
+    if (ln) hipLaunchKernelGGL(ln_kernel(K[0], B), grid, block, (size_t)B * K[0] * 2, (hipStream_t)stream, a);
+    else if (e.gate) hipLaunchKernelGGL(gemv_multi_kernel<true>, grid, block, lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(gemv_multi_kernel<false>, grid, block, lds, (hipStream_t)stream, a);
+    return finish_launch();
 }
 
 }  // namespace
 
 extern "C" int vrwkv_gemv_multi_bf16(int n_jobs, int B, const void* const* W, const void* const* x, const void* const* res,
                                      void* const* y, const int* N, const int* K, const int* act, void* stream) {
-    return launch(n_jobs, B, W, x, res, nullptr, y, N, K, act, nullptr, nullptr, nullptr, 0, stream);
+    return launch(n_jobs, B, W, x, res, y, N, K, act, Extras{}, stream);
 }
 
 extern "C" int vrwkv_gemv_multi_copy_bf16(int n_jobs, int B, const void* const* W, const void* const* x, const void* const* res,
                                           void* const* y, const int* N, const int* K, const int* act, const void* copy_src,
                                           void* copy_dst, long copy_elems, void* stream) {
-    return launch(n_jobs, B, W, x, res, nullptr, y, N, K, act, nullptr, copy_src, copy_dst, copy_elems, stream);
+    Extras e;
+    e.copy_src = copy_src; e.copy_dst = copy_dst; e.copy_elems = copy_elems;
+    return launch(n_jobs, B, W, x, res, y, N, K, act, e, stream);
 }
 
 extern "C" int vrwkv_gemv_gated_copy_bf16(int n_jobs, int B, const void* const* W, const void* const* x, const void* const* res,
                                           const void* const* gate, void* const* y, const int* N, const int* K, const int* act,
                                           const void* copy_src, void* copy_dst, long copy_elems, void* stream) {
     if (!gate) return VRWKV_EINVAL;
-    return launch(n_jobs, B, W, x, res, nullptr, y, N, K, act, nullptr, copy_src, copy_dst, copy_elems, stream, gate);
+    Extras e;
+    e.gate = gate;
+    e.copy_src = copy_src; e.copy_dst = copy_dst; e.copy_elems = copy_elems;
+    return launch(n_jobs, B, W, x, res, y, N, K, act, e, stream);
 }
 
 extern "C" int vrwkv_gemv_ln_multi_bf16(int n_jobs, int B, int K, const void* const* W, const void* x, const void* ln_w,
                                         const void* ln_b, float eps, const void* x_prev, const void* const* mu, void* h_out,
                                         void* const* y, const int* N, const int* act, void* stream) {
-    if (n_jobs <= 0 || n_jobs > GV_MAX_JOBS || !x || !ln_w || !ln_b || !x_prev || !mu || !h_out) return VRWKV_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(ln_w) | reinterpret_cast<uintptr_t>(ln_b) | reinterpret_cast<uintptr_t>(x_prev) |
-         reinterpret_cast<uintptr_t>(h_out)) & 15u) return VRWKV_EALIGN;
+    if (n_jobs <= 0 || n_jobs > GV_MAX_JOBS || hostchk::any_null(x, ln_w, ln_b, x_prev, mu, h_out)) return VRWKV_EINVAL;
+    if (hostchk::any_misaligned(ln_w, ln_b, x_prev, h_out)) return VRWKV_EALIGN;
     const void* xs_[GV_MAX_JOBS];
     int Ks[GV_MAX_JOBS];
     for (int j = 0; j < n_jobs; ++j) { xs_[j] = x; Ks[j] = K; }
     const LnFold ln{(const uint16_t*)ln_w, (const uint16_t*)ln_b, (const uint16_t*)x_prev, (uint16_t*)h_out, eps};
-    return launch(n_jobs, B, W, xs_, nullptr, mu, y, N, Ks, act, &ln, nullptr, nullptr, 0, stream);
+    Extras e;
+    e.ln = &ln; e.mu = mu;
+    return launch(n_jobs, B, W, xs_, nullptr, y, N, Ks, act, e, stream);
 }

@@ -5,16 +5,18 @@
 // v6.xx/src/model.py:137-144), with the per-head state S (fp32, [key i][value j]: the layout of vrwkv_wkv6_forward_state_bf16) read and
 // written in place:
 //     y[j] = sum_i r[i] (u[i] k[i] v[j] + S[i][j]) ;   S[i][j] = S[i][j] w[i] + k[i] v[j]           w = exp(-exp(w_raw))
-// One wave per (b,h): lane j owns value column j.  The 16 KB state tile is staged through LDS with 16-byte coalesced accesses
-// (row stride padded to 65 floats, as wkv7_step.hip); the five 128-byte vectors come in as one 16-byte load per lane.
+// One wave per (b,h): lane j owns value column j.  The 16 KB state tile is staged through LDS (decode_common.h); the five 128-byte
+// vectors come in as one 16-byte load per lane.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
+#include "decode_common.h"
 #include "host_checks.h"
-typedef uint32_t vrwkv_u4 __attribute__((ext_vector_type(4)));
 
 namespace {
+
+using namespace decode;
 
 constexpr int W6_MAX_B = 4;
 constexpr int W6_MAX_H = 128;                  // C = 64 H <= 8192
@@ -32,19 +34,13 @@ __global__ __launch_bounds__(64) void wkv6_step_kernel(int H, const uint16_t* __
     if (l < 40) {                                  // lanes 8 m .. 8 m + 7: vector m, 8 elements each
         const int m = l >> 3, c = (l & 7) * 8;
         const uint16_t* src = m == 0 ? r_ + vb : m == 1 ? k_ + vb : m == 2 ? w_ + vb : m == 3 ? u_ + (size_t)(bh % H) * 64 : v_ + vb;
-        const vrwkv_u4 x = *reinterpret_cast<const vrwkv_u4*>(src + c);
         float* d = &vec[m][c];
-        d[0] = bf16_lo(x.x); d[1] = bf16_hi(x.x); d[2] = bf16_lo(x.y); d[3] = bf16_hi(x.y);
-        d[4] = bf16_lo(x.z); d[5] = bf16_hi(x.z); d[6] = bf16_lo(x.w); d[7] = bf16_hi(x.w);
+        unpack8(ld16(src + c), d);
         if (m == 2)
 #pragma unroll
             for (int e = 0; e < 8; ++e) d[e] = fast_exp(-fast_exp(d[e]));
     }
-    for (int e = l; e < 1024; e += 64) {           // 1024 float4 = the 64x64 tile
-        const float4 x = reinterpret_cast<const float4*>(sp)[e];
-        const int i = e >> 4, c = (e & 15) * 4;
-        S[i][c] = x.x; S[i][c + 1] = x.y; S[i][c + 2] = x.z; S[i][c + 3] = x.w;
-    }
+    for (int e = l; e < STATE_VECS; e += 64) state_put(S, e, reinterpret_cast<const float4*>(sp)[e]);
     __syncthreads();
     const float vj = vec[4][l];
     float y = 0.f;
@@ -57,10 +53,7 @@ __global__ __launch_bounds__(64) void wkv6_step_kernel(int H, const uint16_t* __
     yb[l] = (uint16_t)f32_to_bf16_bits(y);
     __syncthreads();
     if (l < 8) *reinterpret_cast<vrwkv_u4*>(y_ + vb + l * 8) = *reinterpret_cast<const vrwkv_u4*>(&yb[l * 8]);
-    for (int e = l; e < 1024; e += 64) {
-        const int i = e >> 4, c = (e & 15) * 4;
-        reinterpret_cast<float4*>(sp)[e] = make_float4(S[i][c], S[i][c + 1], S[i][c + 2], S[i][c + 3]);
-    }
+    for (int e = l; e < STATE_VECS; e += 64) reinterpret_cast<float4*>(sp)[e] = state_get(S, e);
 }
 
 }  // namespace
@@ -69,8 +62,7 @@ extern "C" int vrwkv_wkv6_step_bf16(int B, int H, const void* r, const void* k, 
                                     float* state, void* y, void* stream) {
     if (B <= 0 || B > W6_MAX_B || H <= 0 || hostchk::any_null(r, k, v, w_raw, u, state, y)) return VRWKV_EINVAL;
     if (H > W6_MAX_H) return VRWKV_ESHAPE;
-    if ((reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(w_raw) |
-         reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(y)) & 15u) return VRWKV_EALIGN;
+    if (hostchk::any_misaligned(r, k, v, w_raw, u, state, y)) return VRWKV_EALIGN;
     hipLaunchKernelGGL(wkv6_step_kernel, dim3((unsigned)(B * H)), dim3(64), 0, (hipStream_t)stream, H, (const uint16_t*)r,
                        (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)w_raw, (const uint16_t*)u, state, (uint16_t*)y);
     return hostchk::finish_launch();

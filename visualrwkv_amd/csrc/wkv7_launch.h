@@ -17,10 +17,10 @@ constexpr long FWD_ISPLIT_MAX_HEADS = 128;
 // segment 1, where the producers have ~1.2k cycles of slack per chunk and the consumers none (128; 1.09 -> 1.04 ms)
 constexpr int BWD_V5_MODE = 2 + 4 + 128;
 
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }      // NULL is not misaligned
+using hostchk::any_misaligned;
 using hostchk::any_null;
 using hostchk::finish_launch;
-template <class... Ptr> inline bool any_misaligned(Ptr... p) { return (... || misaligned(p)); }
+using hostchk::misaligned;
 inline int check_common(int B, int T, int H) {
     if (B <= 0 || T <= 0 || H <= 0) return VRWKV_EINVAL;
     if (T % VRWKV_CHUNK_LEN != 0) return VRWKV_ESHAPE;   // cuda_backward asserts this, wkv7_cuda.cu:136

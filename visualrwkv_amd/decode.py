@@ -8,8 +8,6 @@ Inference only; first-stage LoRA factors are read through cached (N,K)-major cop
 modified in place)."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import hip_lib
@@ -18,38 +16,33 @@ ACT_NONE, ACT_TANH, ACT_SIGMOID, ACT_RELUSQ = 0, 1, 2, 3
 MAX_B = 4
 
 
-def _stream(dev):
-    return hip_lib.launch_stream(dev)
-
-
-def gemv_multi(jobs, B, device):
-    """jobs: list of (W (N,K), x (B,K), res (B,N) or None, act) -> list of y (B,N) bf16, one launch."""
-    n = len(jobs)
-    ys = [torch.empty(B, W.shape[0], dtype=torch.bfloat16, device=device) for W, _, _, _ in jobs]
-    vp = ctypes.c_void_p * n
-    ip = ctypes.c_int * n
-    rc = hip_lib.load().vrwkv_gemv_multi_bf16(
-        n, B, vp(*[W.data_ptr() for W, _, _, _ in jobs]), vp(*[x.data_ptr() for _, x, _, _ in jobs]),
-        vp(*[(r.data_ptr() if r is not None else 0) for _, _, r, _ in jobs]), vp(*[y.data_ptr() for y in ys]),
-        ip(*[W.shape[0] for W, _, _, _ in jobs]), ip(*[W.shape[1] for W, _, _, _ in jobs]), ip(*[a for _, _, _, a in jobs]),
-        _stream(device))
-    hip_lib.check(rc, "vrwkv_gemv_multi_bf16")
+def _gemv(entry, jobs, B, device, gates=None, copy=False):
+    """One launch of a batched-GEMV entry of csrc/gemv_decode.hip: the one place that lays out its job arrays.  jobs: list of
+    (W (N,K), x (B,K), res (B,N) or None, act); gates: the gated entry's (B,N) per job; copy: None or (src, dst) for the entries with the copy side
+    job (dst[:] = src), False for the entry without.  Returns the list of y (B,N) bf16."""
+    Ws, xs, res, acts = zip(*jobs)
+    ys = [torch.empty(B, W.shape[0], dtype=torch.bfloat16, device=device) for W in Ws]
+    args = [len(jobs), B, Ws, xs, res, ys, [W.shape[0] for W in Ws], [W.shape[1] for W in Ws], acts]
+    if gates is not None:
+        args.insert(5, gates)
+    if copy is not False:
+        args += (copy[0], copy[1], copy[0].numel()) if copy else (None, None, 0)
+    hip_lib.launch(entry, *args, device=device)
     return ys
 
 
-def gemv_multi_copy(jobs, B, device, copy_src, copy_dst):
-    """gemv_multi plus the side job copy_dst[:] = copy_src (the carried token-shift row, see gemv_ln_multi)."""
-    n = len(jobs)
-    ys = [torch.empty(B, W.shape[0], dtype=torch.bfloat16, device=device) for W, _, _, _ in jobs]
-    vp = ctypes.c_void_p * n
-    ip = ctypes.c_int * n
-    rc = hip_lib.load().vrwkv_gemv_multi_copy_bf16(
-        n, B, vp(*[W.data_ptr() for W, _, _, _ in jobs]), vp(*[x.data_ptr() for _, x, _, _ in jobs]),
-        vp(*[(r.data_ptr() if r is not None else 0) for _, _, r, _ in jobs]), vp(*[y.data_ptr() for y in ys]),
-        ip(*[W.shape[0] for W, _, _, _ in jobs]), ip(*[W.shape[1] for W, _, _, _ in jobs]), ip(*[a for _, _, _, a in jobs]),
-        copy_src.data_ptr(), copy_dst.data_ptr(), copy_src.numel(), _stream(device))
-    hip_lib.check(rc, "vrwkv_gemv_multi_copy_bf16")
-    return ys
+def gemv_multi(jobs, B, device, copy=None):
+    """jobs: list of (W (N,K), x (B,K), res (B,N) or None, act) -> list of y (B,N) bf16, one launch.
+    copy: optional (src, dst), dst[:] = src as the side job (the carried token-shift row, see gemv_ln_multi)."""
+    if copy is None:
+        return _gemv("vrwkv_gemv_multi_bf16", jobs, B, device)
+    return _gemv("vrwkv_gemv_multi_copy_bf16", jobs, B, device, copy=copy)
+
+
+def gemv_gated(jobs, B, device, copy=None):
+    """jobs: list of (W (N,K), x (B,K), res (B,N) or None, gate (B,N), act) -> list of y = res + gate * act(W x), one launch.
+    copy: optional (src, dst), dst[:] = src as the side job."""
+    return _gemv("vrwkv_gemv_gated_copy_bf16", [(W, x, r, a) for W, x, r, _, a in jobs], B, device, gates=[j[3] for j in jobs], copy=copy)
 
 
 def ln_fold_supported(C):
@@ -61,29 +54,19 @@ def gemv_ln_multi(jobs, x, ln, x_prev):
     h = LayerNorm(x), one launch.  Returns (ys, h); x_prev is NOT updated (the caller hands h to a later launch's
     copy side job, because workgroups of this launch read x_prev until it ends)."""
     B, K = x.shape
-    n = len(jobs)
-    ys = [torch.empty(B, W.shape[0], dtype=torch.bfloat16, device=x.device) for W, _, _ in jobs]
+    Ws, mus, acts = zip(*jobs)
+    ys = [torch.empty(B, W.shape[0], dtype=torch.bfloat16, device=x.device) for W in Ws]
     h = torch.empty_like(x)
-    vp = ctypes.c_void_p * n
-    ip = ctypes.c_int * n
-    rc = hip_lib.load().vrwkv_gemv_ln_multi_bf16(
-        n, B, K, vp(*[W.data_ptr() for W, _, _ in jobs]), x.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps),
-        x_prev.data_ptr(), vp(*[m.data_ptr() for _, m, _ in jobs]), h.data_ptr(), vp(*[y.data_ptr() for y in ys]),
-        ip(*[W.shape[0] for W, _, _ in jobs]), ip(*[a for _, _, a in jobs]), _stream(x.device))
-    hip_lib.check(rc, "vrwkv_gemv_ln_multi_bf16")
+    hip_lib.launch("vrwkv_gemv_ln_multi_bf16", len(jobs), B, K, Ws, x, ln.weight, ln.bias, float(ln.eps), x_prev, mus, h, ys,
+                   [W.shape[0] for W in Ws], acts, device=x.device)
     return ys, h
 
 
 def ln_mix(x, ln, x_prev, mus):
     """x (B,C) -> [LN(x) + (x_prev - LN(x)) * mu for mu in mus]; x_prev (B,C) is replaced by LN(x) in place."""
     B, C = x.shape
-    n = len(mus)
     outs = [torch.empty_like(x) for _ in mus]
-    vp = ctypes.c_void_p * n
-    rc = hip_lib.load().vrwkv_decode_ln_mix_bf16(B, C, n, x.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), float(ln.eps),
-                                                 x_prev.data_ptr(), vp(*[m.data_ptr() for m in mus]),
-                                                 vp(*[o.data_ptr() for o in outs]), _stream(x.device))
-    hip_lib.check(rc, "vrwkv_decode_ln_mix_bf16")
+    hip_lib.launch("vrwkv_decode_ln_mix_bf16", B, C, len(mus), x, ln.weight, ln.bias, float(ln.eps), x_prev, list(mus), outs, device=x.device)
     return outs
 
 
@@ -95,17 +78,11 @@ def tmix_head(m, r, k, v, v_first, hidden, S, carry=None):
     names = ("w2", "a2", "g2") + (("v2",) if v_first is not None else ())
     t = _transposed(m, names, "_decode_cache2")
     W2 = [t[n] for n in names]                       # (C, D): a channel's D weights are contiguous
-    n = len(W2)
     out = torch.empty_like(r)
-    vp = ctypes.c_void_p * n
-    ip = ctypes.c_int * n
-    rc = hip_lib.load().vrwkv_decode_tmix_head_bf16(
-        B, C // 64, r.data_ptr(), k.data_ptr(), v.data_ptr(), v_first.data_ptr() if v_first is not None else 0,
-        vp(*[h.data_ptr() for h in hidden]), vp(*[w.data_ptr() for w in W2]), ip(*[w.shape[1] for w in W2]),
-        m.w0.data_ptr(), m.a0.data_ptr(), m.v0.data_ptr() if v_first is not None else 0, m.k_k.data_ptr(), m.k_a.data_ptr(),
-        m.r_k.data_ptr(), m.ln_x.weight.data_ptr(), m.ln_x.bias.data_ptr(), float(m.ln_x.eps), S.data_ptr(), out.data_ptr(),
-        carry[0].data_ptr() if carry else 0, carry[1].data_ptr() if carry else 0, _stream(r.device))
-    hip_lib.check(rc, "vrwkv_decode_tmix_head_bf16")
+    src, dst = carry if carry else (None, None)
+    hip_lib.launch("vrwkv_decode_tmix_head_bf16", B, C // 64, r, k, v, v_first, list(hidden), W2, [w.shape[1] for w in W2], m.w0, m.a0,
+                   m.v0 if v_first is not None else None, m.k_k, m.k_a, m.r_k, m.ln_x.weight, m.ln_x.bias, float(m.ln_x.eps), S, out, src, dst,
+                   device=r.device)
     return out
 
 
@@ -160,7 +137,7 @@ def block_decode(block, x, v_first, state):
     (x,) = gemv_multi([(att.output.weight, y, x, ACT_NONE)], B, dev)                                # x + output(y)
     if fold:
         (kk,), h = gemv_ln_multi([(ffn.key.weight, ffn.x_k, ACT_RELUSQ)], x, block.ln2, state.ffn_x[lid])
-        (x2,) = gemv_multi_copy([(ffn.value.weight, kk, x, ACT_NONE)], B, dev, h, state.ffn_x[lid])
+        (x2,) = gemv_multi([(ffn.value.weight, kk, x, ACT_NONE)], B, dev, copy=(h, state.ffn_x[lid]))
     else:
         (kx,) = ln_mix(x, block.ln2, state.ffn_x[lid], [ffn.x_k])
         (kk,) = gemv_multi([(ffn.key.weight, kx, None, ACT_RELUSQ)], B, dev)

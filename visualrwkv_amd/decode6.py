@@ -13,12 +13,10 @@ Widths the LayerNorm fold does not cover (C < 512, C > 4096) spend a separate ln
 factors are read through cached (N,K)-major copies (decode._transposed), time_maa_w2 and time_decay_w2 as stored."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from . import hip_lib
-from .decode import (ACT_NONE, ACT_RELUSQ, ACT_SIGMOID, ACT_TANH, MAX_B, _bf16_contig, _stream, _transposed, gemv_ln_multi, gemv_multi,
+from . import decode, hip_lib
+from .decode import (ACT_NONE, ACT_RELUSQ, ACT_SIGMOID, ACT_TANH, _bf16_contig, _transposed, gemv_gated, gemv_ln_multi, gemv_multi, head_decode,  # noqa: F401
                      ln_fold_supported, ln_mix)
 
 MAX_C = 8192
@@ -27,19 +25,15 @@ MAA = ("time_maa_w", "time_maa_k", "time_maa_v", "time_maa_r", "time_maa_g")    
 
 def supported(x):
     """x (B,1,C): one bf16 token per sample on the GPU, within the kernels' bounds (those of fused.supported6's width)."""
-    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3 and x.shape[1] == 1 and x.shape[0] <= MAX_B
-            and x.shape[2] % 64 == 0 and x.shape[2] <= MAX_C)
+    return decode.supported(x) and x.shape[2] % 64 == 0 and x.shape[2] <= MAX_C
 
 
 def ddlerp(att, h, x_prev, hid):
     """The five inputs xw, xk, xv, xr, xg of RWKV_Tmix_x060.mix for one token; x_prev (B,C) is replaced by h in place."""
     B, C = h.shape
     outs = [torch.empty_like(h) for _ in MAA]
-    vp = ctypes.c_void_p * 5
-    rc = hip_lib.load().vrwkv_decode6_ddlerp_bf16(B, C, att.time_maa_w2.shape[1], h.data_ptr(), x_prev.data_ptr(), hid.data_ptr(),
-                                                  att.time_maa_w2.data_ptr(), vp(*[getattr(att, n).data_ptr() for n in MAA]),
-                                                  vp(*[o.data_ptr() for o in outs]), _stream(h.device))
-    hip_lib.check(rc, "vrwkv_decode6_ddlerp_bf16")
+    hip_lib.launch("vrwkv_decode6_ddlerp_bf16", B, C, att.time_maa_w2.shape[1], h, x_prev, hid, att.time_maa_w2, [getattr(att, n) for n in MAA], outs,
+                   device=h.device)
     return outs
 
 
@@ -47,28 +41,9 @@ def tmix_head(att, r, k, v, g, hid, S):
     """Everything of RWKV_Tmix_x060.forward between the projections and the output projection, for one token; S in place."""
     B, C = r.shape
     out = torch.empty_like(r)
-    rc = hip_lib.load().vrwkv_decode6_tmix_head_bf16(
-        B, C // 64, att.time_decay_w2.shape[0], r.data_ptr(), k.data_ptr(), v.data_ptr(), g.data_ptr(), hid.data_ptr(),
-        att.time_decay_w2.data_ptr(), att.time_decay.data_ptr(), att.time_faaaa.data_ptr(), att.ln_x.weight.data_ptr(),
-        att.ln_x.bias.data_ptr(), float(att.ln_x.eps), S.data_ptr(), out.data_ptr(), _stream(r.device))
-    hip_lib.check(rc, "vrwkv_decode6_tmix_head_bf16")
+    hip_lib.launch("vrwkv_decode6_tmix_head_bf16", B, C // 64, att.time_decay_w2.shape[0], r, k, v, g, hid, att.time_decay_w2, att.time_decay,
+                   att.time_faaaa, att.ln_x.weight, att.ln_x.bias, float(att.ln_x.eps), S, out, device=r.device)
     return out
-
-
-def gemv_gated(jobs, B, device, copy=None):
-    """jobs: list of (W (N,K), x (B,K), res (B,N) or None, gate (B,N), act) -> list of y = res + gate * act(W x), one launch.
-    copy: optional (src, dst), dst[:] = src as the side job."""
-    n = len(jobs)
-    ys = [torch.empty(B, j[0].shape[0], dtype=torch.bfloat16, device=device) for j in jobs]
-    vp = ctypes.c_void_p * n
-    ip = ctypes.c_int * n
-    rc = hip_lib.load().vrwkv_gemv_gated_copy_bf16(
-        n, B, vp(*[j[0].data_ptr() for j in jobs]), vp(*[j[1].data_ptr() for j in jobs]),
-        vp(*[(j[2].data_ptr() if j[2] is not None else 0) for j in jobs]), vp(*[j[3].data_ptr() for j in jobs]), vp(*[y.data_ptr() for y in ys]),
-        ip(*[j[0].shape[0] for j in jobs]), ip(*[j[0].shape[1] for j in jobs]), ip(*[j[4] for j in jobs]),
-        copy[0].data_ptr() if copy else 0, copy[1].data_ptr() if copy else 0, copy[0].numel() if copy else 0, _stream(device))
-    hip_lib.check(rc, "vrwkv_gemv_gated_copy_bf16")
-    return ys
 
 
 @torch.no_grad()
@@ -108,11 +83,3 @@ def block_decode(block, x, state):
         (x2,) = gemv_gated([(ffn.value.weight, kk, x, rr, ACT_NONE)], B, dev)                        # x + sigmoid(r) * value(relu(key)^2)
     return x2.view(B, 1, C)
 
-
-@torch.no_grad()
-def head_decode(rwkv, x):
-    """ln_out + head for one token: x (B,1,C) -> logits (B,V)."""
-    B, _, C = x.shape
-    h = rwkv.ln_out(x).view(B, C)
-    (logits,) = gemv_multi([(rwkv.head.weight, h, None, ACT_NONE)], B, x.device)
-    return logits

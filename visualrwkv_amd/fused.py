@@ -7,7 +7,6 @@ MI355X -- anything else raises.
 """
 from __future__ import annotations
 
-import ctypes
 import os
 
 import torch
@@ -30,12 +29,7 @@ def _chk(*ts):
                              f"(got {t.dtype}, cuda={t.is_cuda}, contiguous={t.is_contiguous()})")
 
 
-def _ptr_array(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else 0
+_ptr_array, _p = hip_lib.array, hip_lib.p
 
 
 def _ws(ntok, C, nvec, device):
@@ -44,11 +38,8 @@ def _ws(ntok, C, nvec, device):
 
 
 def _glue(name, *args, like):
-    """One launch of the library entry `name` on PyTorch's current stream of like's device.  The entry gets `args` -- tensors as pointers, None
-    as NULL, lists of tensors as pointer arrays, numbers as they are -- then the stream; a code other than 0 raises (hip_lib.check)."""
-    Tensor = torch.Tensor                     # the common case first: this runs once per launch, 26 arguments for kva's backward
-    conv = [a.data_ptr() if isinstance(a, Tensor) else 0 if a is None else _ptr_array(a) if isinstance(a, (list, tuple)) else a for a in args]
-    hip_lib.check(getattr(hip_lib.load(), name)(*conv, _stream(like)), name)
+    """One launch of the library entry `name` on PyTorch's current stream of like's device: hip_lib.launch says how `args` reach the entry."""
+    hip_lib.launch(name, *args, device=like.device)
 
 
 def _grad_rows(ntok, C, nvec, device):

@@ -208,6 +208,51 @@ def check(code: int, what: str) -> None:
         raise RuntimeError(f"{what} failed: {msg} (code {code})")
 
 
+def p(t) -> int:
+    """A tensor's address, NULL for None."""
+    return t.data_ptr() if t is not None else 0
+
+
+class _ArrayTypes(dict):
+    """ctypes array types of one element type by length, made once."""
+    def __init__(self, ctype):
+        self.ctype = ctype
+
+    def __missing__(self, n):
+        t = self[n] = self.ctype * n
+        return t
+
+
+_INT_ARRAYS, _PTR_ARRAYS = _ArrayTypes(_c_int), _ArrayTypes(_c_void_p)
+
+
+def array(vs):
+    """A C array for an entry: of ints from a list of ints, else of pointers from a list of tensors (None: NULL)."""
+    n = len(vs)
+    if n and type(vs[0]) is int:
+        return _INT_ARRAYS[n](*vs)
+    return _PTR_ARRAYS[n](*[t.data_ptr() if t is not None else 0 for t in vs])
+
+
+_Tensor = _Parameter = None
+
+
+def launch(name: str, *args, device) -> None:
+    """One launch of the library entry `name` on PyTorch's current stream of `device`: the one way the wrappers call an entry.  The entry gets
+    `args` -- tensors as pointers, None as NULL, lists as C arrays (array()), numbers as they are -- then the stream; a code other than 0 raises
+    (check)."""
+    global _Tensor, _Parameter
+    if _Tensor is None:
+        from torch import Tensor as _Tensor
+        from torch.nn import Parameter as _Parameter
+    Tensor, Parameter = _Tensor, _Parameter
+    # This runs once per launch (26 arguments for kva's backward, seven arrays for a decode GEMV) and is what an eager decode step pays per kernel:
+    # the common case first and by exact type -- a tensor or a parameter -- then lists; isinstance only for what is left (tensor subclasses, numbers).
+    conv = [a.data_ptr() if (t := type(a)) is Tensor or t is Parameter else array(a) if t is list or t is tuple else 0 if a is None
+            else a.data_ptr() if isinstance(a, Tensor) else a for a in args]
+    check(getattr(load(), name)(*conv, launch_stream(device)), name)
+
+
 def launch_stream(device) -> int:
     """Raw handle of PyTorch's current stream on `device` for a ctypes launch.  The kernels are launched on that stream,
     which belongs to `device`: HIP requires it to be the calling thread's current device (one process per GPU always is).
@@ -218,4 +263,5 @@ def launch_stream(device) -> int:
     if dev.index is not None and dev.index != torch.cuda.current_device():
         raise RuntimeError(f"visualrwkv_amd: tensors live on {dev} but the current device is cuda:{torch.cuda.current_device()}; "
                            f"wrap the call in `with torch.cuda.device({dev.index}):`")
-    return torch.cuda.current_stream(dev).cuda_stream
+    # the raw handle without building a torch.cuda.Stream around it: this runs once per launch
+    return torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
