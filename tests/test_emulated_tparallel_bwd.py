@@ -56,7 +56,6 @@ def test_host_function_on_the_emulator(emu_lib, monkeypatch):
     """visualrwkv_amd.wkv7.wkv7_backward_tparallel itself (segment views, M_p, scan, two launches), with the two C-ABI
     entries it calls redirected to the emulated kernels -- the host logic cannot run on a GPU in this suite."""
     import contextlib
-    from types import SimpleNamespace
 
     from visualrwkv_amd import hip_lib, wkv7
 
@@ -80,7 +79,7 @@ def test_host_function_on_the_emulator(emu_lib, monkeypatch):
 
     monkeypatch.setattr(hip_lib, "load", lambda: Shim)
     monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: SimpleNamespace(cuda_stream=0))
+    monkeypatch.setattr(hip_lib, "launch_stream", lambda device: 0)
     B, T, H, nseg = 2, 64, 1, 2
     w, q, k, v, z, a, dy = make_inputs(B, T, H, seed=5)
     y = torch.zeros_like(v)

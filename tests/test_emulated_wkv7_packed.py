@@ -14,7 +14,6 @@ A packed row is several samples end to end, each a whole number of 16-token chun
 """
 import contextlib
 import ctypes
-from types import SimpleNamespace
 
 import pytest
 import torch
@@ -205,7 +204,7 @@ def emulated_op(emu_lib, monkeypatch):
     monkeypatch.setattr(hip_lib, "load", lambda: _shim(emu_lib))
     monkeypatch.setattr(wkv7, "_native", lambda t: True)
     monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: SimpleNamespace(cuda_stream=0))
+    monkeypatch.setattr(hip_lib, "launch_stream", lambda device: 0)
     return wkv7
 
 

@@ -3,7 +3,6 @@ csrc/wkv7_bwd_v8.h (schedules 8 and 9), the C entry vrwkv_wkv7_backward_state_bf
 against fp64 autograd through the oracle recurrence (tests/state_ref.py)."""
 import contextlib
 import ctypes
-from types import SimpleNamespace
 
 import pytest
 import torch
@@ -107,7 +106,7 @@ def emulated_op(emu_lib, monkeypatch):
     monkeypatch.setattr(hip_lib, "load", lambda: _shim(emu_lib))
     monkeypatch.setattr(wkv7, "_native", lambda t: True)
     monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: SimpleNamespace(cuda_stream=0))
+    monkeypatch.setattr(hip_lib, "launch_stream", lambda device: 0)
     return wkv7
 
 

@@ -56,3 +56,32 @@ def test_adamw_kernel_matches_torch_adamw_over_5_steps():
     for b in eng.buckets:
         s = b.start + eng.rank * b.piece
         assert torch.allclose(b.master, flat_ref[s:s + b.piece], rtol=2e-5, atol=2e-6)
+
+
+def test_adamw_with_a_host_side_scale_matches_torch_adamw():
+    """Zero1Engine._adamw with the gradient scale formed on the host: vrwkv_adamw_step_bf16 (step() on the GPU forms the clip factor on the
+    device and takes the _clip entry, so only a direct call gets here).  One update of three buckets, the weight-decay boundary inside the
+    last one, against fp32 torch.optim.AdamW on the same scaled bf16 gradients; the fp32 masters as in the test above."""
+    from visualrwkv_amd.dp import Zero1Engine
+    torch.manual_seed(0)
+    m = nn.Sequential(nn.Linear(64, 64), nn.LayerNorm(64)).cuda().bfloat16()
+    lr, scale = 3e-3, 0.37
+    eng = Zero1Engine(m, lr=lr, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.1, grad_clip=1.0, bucket_mb=0.004)
+    assert len(eng.buckets) == 3 and eng.buckets[-1].start < eng.wd_boundary < eng.numel and eng.world == 1
+    g = torch.Generator(device="cuda").manual_seed(1)
+    eng.flat_grad.copy_(torch.randn(eng.numel, device="cuda", generator=g).bfloat16())
+    master = torch.cat([b.master for b in eng.buckets])             # one rank: a piece is its whole bucket
+    ref = [master[:eng.wd_boundary].clone().requires_grad_(True), master[eng.wd_boundary:].clone().requires_grad_(True)]
+    opt = torch.optim.AdamW([{"params": ref[:1], "weight_decay": 0.1}, {"params": ref[1:], "weight_decay": 0.0}],
+                            lr=lr, betas=(0.9, 0.99), eps=1e-8)
+    gf = eng.flat_grad.float() * scale
+    ref[0].grad, ref[1].grad = gf[:eng.wd_boundary].clone(), gf[eng.wd_boundary:].clone()
+    opt.step()
+    eng.step_count = 1
+    for b in eng.buckets:
+        eng._adamw(b, lr, scale)
+    flat_ref = torch.cat(ref).detach()
+    assert not torch.equal(flat_ref, master)
+    for b in eng.buckets:
+        assert torch.allclose(b.master, flat_ref[b.start:b.start + b.piece], rtol=2e-5, atol=2e-6)
+        assert torch.equal(eng.flat_param[b.start:b.start + b.piece], b.master.bfloat16())      # published: the rounded master

@@ -466,8 +466,7 @@ class Zero1Engine:
     def _sqnorm(self, g, out):
         if self.on_gpu and g.dtype == torch.bfloat16 and g.numel() % 8 == 0:
             from . import hip_lib
-            rc = hip_lib.load().vrwkv_sqnorm_bf16(g.numel(), g.data_ptr(), out.data_ptr(), hip_lib.launch_stream(self.device))
-            hip_lib.check(rc, "vrwkv_sqnorm_bf16")
+            hip_lib.launch("vrwkv_sqnorm_bf16", g.numel(), g, out, device=self.device)
         else:
             out += g.float().pow(2).sum()
 
@@ -478,18 +477,13 @@ class Zero1Engine:
         b1, b2 = self.betas
         if self.on_gpu and g.dtype == torch.bfloat16:
             from . import hip_lib
-            st = hip_lib.launch_stream(self.device)
+            lr = float(lr)                        # a number: launch would take a tensor for a pointer
             if scale is None:
-                rc = hip_lib.load().vrwkv_adamw_step_clip_bf16(
-                    b.piece, b.master.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), g.data_ptr(), p.data_ptr(),
-                    lr, b1, b2, self.eps, self.weight_decay, self.step_count, self._sq.data_ptr(), inv_world, clip, off,
-                    self.wd_boundary, st)
-                hip_lib.check(rc, "vrwkv_adamw_step_clip_bf16")
-                return
-            rc = hip_lib.load().vrwkv_adamw_step_bf16(
-                b.piece, b.master.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), g.data_ptr(), p.data_ptr(),
-                lr, b1, b2, self.eps, self.weight_decay, self.step_count, scale, off, self.wd_boundary, st)
-            hip_lib.check(rc, "vrwkv_adamw_step_bf16")
+                hip_lib.launch("vrwkv_adamw_step_clip_bf16", b.piece, b.master, b.m, b.v, g, p, lr, b1, b2, self.eps, self.weight_decay,
+                               self.step_count, self._sq, inv_world, clip, off, self.wd_boundary, device=self.device)
+            else:
+                hip_lib.launch("vrwkv_adamw_step_bf16", b.piece, b.master, b.m, b.v, g, p, lr, b1, b2, self.eps, self.weight_decay,
+                               self.step_count, scale, off, self.wd_boundary, device=self.device)
             return
         # host restatement of the kernel (CPU tests of the distributed logic)
         gf = g.float() * scale

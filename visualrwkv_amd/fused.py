@@ -16,10 +16,6 @@ from . import gemm_tuning, hip_lib
 from .wkv7 import RUN_CUDA_RWKV7g, RUN_CUDA_RWKV7g_packed, RUN_CUDA_RWKV7g_state
 
 
-def _stream(t):
-    return hip_lib.launch_stream(t.device)
-
-
 def _chk(*ts):
     for t in ts:
         if t is None:
@@ -29,16 +25,14 @@ def _chk(*ts):
                              f"(got {t.dtype}, cuda={t.is_cuda}, contiguous={t.is_contiguous()})")
 
 
-_ptr_array, _p = hip_lib.array, hip_lib.p
-
-
 def _ws(ntok, C, nvec, device):
     n = hip_lib.load().vrwkv_param_grad_ws_floats(ntok, C, nvec)
     return torch.empty(n, dtype=torch.float32, device=device)
 
 
 def _glue(name, *args, like):
-    """One launch of the library entry `name` on PyTorch's current stream of like's device: hip_lib.launch says how `args` reach the entry."""
+    """One launch of the library entry `name` on PyTorch's current stream of like's device -- read now, so under `torch.cuda.stream(side)` it is the
+    side stream: hip_lib.launch says how `args` reach the entry."""
     hip_lib.launch(name, *args, device=like.device)
 
 
@@ -68,15 +62,12 @@ def wgrad_skinny(x2d, dy2d):
     M, K = x2d.shape
     N = dy2d.shape[1]
     wide, narrow, transposed = (x2d, dy2d, 0) if K >= N else (dy2d, x2d, 1)
-    lib = hip_lib.load()
-    nws = lib.vrwkv_wgrad_skinny_ws_floats(M, wide.shape[1], narrow.shape[1])
+    nws = hip_lib.load().vrwkv_wgrad_skinny_ws_floats(M, wide.shape[1], narrow.shape[1])
     if nws < 0:
         raise ValueError(f"wgrad_skinny: unsupported shape ({M},{K}) x ({M},{N})")
     ws = torch.empty(nws, dtype=torch.float32, device=x2d.device)
     out = torch.empty(K, N, dtype=torch.bfloat16, device=x2d.device)
-    rc = lib.vrwkv_wgrad_skinny_bf16(M, wide.shape[1], narrow.shape[1], wide.data_ptr(), narrow.data_ptr(), out.data_ptr(),
-                                     transposed, ws.data_ptr(), _stream(x2d))
-    hip_lib.check(rc, "vrwkv_wgrad_skinny_bf16")
+    _glue("vrwkv_wgrad_skinny_bf16", M, wide.shape[1], narrow.shape[1], wide, narrow, out, transposed, ws, like=x2d)
     return out
 
 
@@ -103,8 +94,7 @@ def skinny_up(a2d, w, w_is_CxR):
     M, R = a2d.shape
     C = w.shape[0] if w_is_CxR else w.shape[1]
     out = torch.empty(M, C, dtype=torch.bfloat16, device=a2d.device)
-    rc = hip_lib.load().vrwkv_skinny_up_bf16(M, R, C, a2d.data_ptr(), w.data_ptr(), int(bool(w_is_CxR)), out.data_ptr(), _stream(a2d))
-    hip_lib.check(rc, "vrwkv_skinny_up_bf16")
+    _glue("vrwkv_skinny_up_bf16", M, R, C, a2d, w, int(bool(w_is_CxR)), out, like=a2d)
     return out
 
 
@@ -180,15 +170,13 @@ def wgrad_big(dy2d, x2d, out=None):
     csrc/wgrad_big.h instead of the library's N,T-class kernel; `out`: a contiguous (N,K) bf16 view to write into."""
     M, N = dy2d.shape
     K = x2d.shape[1]
-    lib = hip_lib.load()
-    nws = lib.vrwkv_wgrad_big_ws_floats(M, N, K)
+    nws = hip_lib.load().vrwkv_wgrad_big_ws_floats(M, N, K)
     if nws < 0:
         raise ValueError(f"wgrad_big: unsupported shape ({M},{N}) x ({M},{K})")
     ws = torch.empty(nws, dtype=torch.float32, device=dy2d.device) if nws else None
     if out is None:
         out = torch.empty(N, K, dtype=torch.bfloat16, device=dy2d.device)
-    rc = lib.vrwkv_wgrad_big_bf16(M, N, K, dy2d.data_ptr(), x2d.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else 0, _stream(dy2d))
-    hip_lib.check(rc, "vrwkv_wgrad_big_bf16")
+    _glue("vrwkv_wgrad_big_bf16", M, N, K, dy2d, x2d, out, ws, like=dy2d)
     return out
 
 
@@ -318,8 +306,7 @@ def transpose2d(w):
     """w.t().contiguous() for a 2-D bf16 matrix: tiled HIP kernel when both sides are multiples of 64 (3-4x torch's copy)."""
     if w.is_cuda and w.dtype == torch.bfloat16 and w.dim() == 2 and w.is_contiguous() and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0:
         out = torch.empty(w.shape[1], w.shape[0], dtype=w.dtype, device=w.device)
-        hip_lib.check(hip_lib.load().vrwkv_transpose_bf16(w.shape[0], w.shape[1], w.data_ptr(), out.data_ptr(), _stream(w)),
-                      "vrwkv_transpose_bf16")
+        _glue("vrwkv_transpose_bf16", w.shape[0], w.shape[1], w, out, like=w)
         return out
     return w.t().contiguous()
 
@@ -596,11 +583,8 @@ def _add_ln_bwd(dy, d_xn, xn, mean, rstd, wc):
     ntok = xn.numel() // C
     dx = torch.empty_like(xn)
     dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
-    lib = hip_lib.load()
-    ws = torch.empty(lib.vrwkv_add_ln_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
-    rc = lib.vrwkv_add_ln_bwd_bf16(ntok, C, dy.data_ptr(), _p(d_xn), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                   wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
-    hip_lib.check(rc, "vrwkv_add_ln_bwd_bf16")
+    ws = torch.empty(hip_lib.load().vrwkv_add_ln_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
+    _glue("vrwkv_add_ln_bwd_bf16", ntok, C, dy, d_xn, xn, mean, rstd, wc, dx, dwb, ws, like=xn)
     return dx, dwb
 
 
@@ -619,10 +603,7 @@ class _AddLN(torch.autograd.Function):
         x, delta, (wc, bc), xn, mean, rstd = _ln_fwd_pre("add_ln", x, delta, (w, b))
         C = x.shape[-1]
         y = torch.empty_like(x)
-        rc = hip_lib.load().vrwkv_add_ln_fwd_bf16(x.numel() // C, C, float(eps), x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
-                                                  xn.data_ptr() if delta is not None else 0, y.data_ptr(),
-                                                  mean.data_ptr(), rstd.data_ptr(), _stream(x))
-        hip_lib.check(rc, "vrwkv_add_ln_fwd_bf16")
+        _glue("vrwkv_add_ln_fwd_bf16", x.numel() // C, C, float(eps), x, delta, wc, bc, xn if delta is not None else None, y, mean, rstd, like=x)
         ctx.save_for_backward(xn, mean, rstd, wc)
         ctx.has_delta = delta is not None
         if delta is None:
@@ -658,9 +639,8 @@ def add_ln_infer(x, delta, dscale, ln):
     _chk(x, delta, ln.weight, ln.bias, dscale)
     xn = torch.empty_like(x) if delta is not None else x
     y = torch.empty_like(x)
-    rc = hip_lib.load().vrwkv_add_ln_scaled_fwd_bf16(x.numel() // C, C, float(ln.eps), x.data_ptr(), _p(delta), _p(dscale), ln.weight.data_ptr(),
-                                                     ln.bias.data_ptr(), xn.data_ptr() if delta is not None else 0, y.data_ptr(), _stream(x))
-    hip_lib.check(rc, "vrwkv_add_ln_scaled_fwd_bf16")
+    _glue("vrwkv_add_ln_scaled_fwd_bf16", x.numel() // C, C, float(ln.eps), x, delta, dscale, ln.weight, ln.bias, xn if delta is not None else None, y,
+          like=x)
     return xn, y
 
 
@@ -692,13 +672,11 @@ class _AddLnMix(torch.autograd.Function):
         _chk(yp)
         outs = [torch.empty_like(x) for _ in mus]
         y_last = torch.empty(B, C, dtype=torch.bfloat16, device=x.device) if want_last else None
-        lib = hip_lib.load()
-        head = (B * T, T, C, float(eps), M, x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(), _ptr_array(mus_c),
-                xn.data_ptr() if delta is not None else 0, _ptr_array(outs), mean.data_ptr(), rstd.data_ptr())
+        head = (B * T, T, C, float(eps), M, x, delta, wc, bc, mus_c, xn if delta is not None else None, outs, mean, rstd)
         if carry:
-            hip_lib.check(lib.vrwkv_ln_mix_fwd_carry_bf16(*head, _p(yp), _p(y_last), _stream(x)), "vrwkv_ln_mix_fwd_carry_bf16")
+            _glue("vrwkv_ln_mix_fwd_carry_bf16", *head, yp, y_last, like=x)
         else:
-            hip_lib.check(lib.vrwkv_ln_mix_fwd_packed_bf16(*head, _p(first), _stream(x)), "vrwkv_ln_mix_fwd_packed_bf16")
+            _glue("vrwkv_ln_mix_fwd_packed_bf16", *head, first, like=x)
         ctx.save_for_backward(xn, mean, rstd, wc, bc, *mus_c, *([yp] if yp is not None else []))
         ctx.first, ctx.carry, ctx.want_last, ctx.has_prev = first, carry, want_last, yp is not None
         ctx.prev_dtype = y_prev.dtype if y_prev is not None else None
@@ -725,22 +703,17 @@ class _AddLnMix(torch.autograd.Function):
         ntok = B * T
         dmu = torch.empty(M, C, dtype=torch.float32, device=xn.device)
         dy_prev = torch.empty(B, C, dtype=torch.float32, device=xn.device) if (yp is not None and ctx.needs_input_grad[7]) else None
-        lib = hip_lib.load()
-        head = (ntok, T, C, M, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wc.data_ptr(), bc.data_ptr(), _ptr_array(mus_c), _ptr_array(douts[:M]), _p(second))
-        variant = (_p(yp), _p(dy_last), _p(dy_prev)) if ctx.carry else (_p(ctx.first),)
+        head = (ntok, T, C, M, xn, mean, rstd, wc, bc, mus_c, douts[:M], second)
+        variant = (yp, dy_last, dy_prev) if ctx.carry else (ctx.first,)
         if M == 1:
             dx = torch.empty_like(xn)
             dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
-            ws = torch.empty(lib.vrwkv_ln_mix_ws_floats(ntok, C, M), dtype=torch.float32, device=xn.device)
-            entry = "vrwkv_ln_mix_bwd_carry_bf16" if ctx.carry else "vrwkv_ln_mix_bwd_packed_bf16"
-            rc = getattr(lib, entry)(*head, _p(d_xn), *variant, dx.data_ptr(), dwb.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, entry)
+            ws = torch.empty(hip_lib.load().vrwkv_ln_mix_ws_floats(ntok, C, M), dtype=torch.float32, device=xn.device)
+            _glue("vrwkv_ln_mix_bwd_carry_bf16" if ctx.carry else "vrwkv_ln_mix_bwd_packed_bf16", *head, d_xn, *variant, dx, dwb, dmu, ws, like=xn)
         else:       # six lerps: their backward with the LayerNorm output recomputed in place of a stored one, then the LayerNorm's
             dy = torch.empty_like(xn)
             ws = _ws(ntok, C, M, xn.device)
-            entry = "vrwkv_mix_bwd_ln_carry_bf16" if ctx.carry else "vrwkv_mix_bwd_ln_packed_bf16"
-            rc = getattr(lib, entry)(*head, *variant, dy.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
-            hip_lib.check(rc, entry)
+            _glue("vrwkv_mix_bwd_ln_carry_bf16" if ctx.carry else "vrwkv_mix_bwd_ln_packed_bf16", *head, *variant, dy, dmu, ws, like=xn)
             dx, dwb = _add_ln_bwd(dy, d_xn, xn, mean, rstd, wc)
         dwb, dmus = _param_grads(dwb, dmu, wc, xn, ctx.mu_shapes)
         return (dx, (dx if ctx.has_delta else None), dwb[0], dwb[1], None, None, None, dy_prev.to(ctx.prev_dtype) if dy_prev is not None else None, None, *dmus)
@@ -822,10 +795,8 @@ class _AddLnMixRouted(torch.autograd.Function):
         ws, bs, mus = params[0:2], params[2:4], params[4:6]
         ntok = B * T
         out = torch.empty(ntok, C, dtype=x.dtype, device=x.device)
-        rc = hip_lib.load().vrwkv_ln_mix_routed_fwd_bf16(ntok, T, C, float(eps), x.data_ptr(), _p(delta), _ptr_array(ws), _ptr_array(bs), _ptr_array(mus),
-                                                         xn.data_ptr() if delta is not None else 0, out.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                         _p(first), plan.sel.data_ptr(), plan.pos.data_ptr(), 4, _stream(x))
-        hip_lib.check(rc, "vrwkv_ln_mix_routed_fwd_bf16")
+        _glue("vrwkv_ln_mix_routed_fwd_bf16", ntok, T, C, float(eps), x, delta, ws, bs, mus, xn if delta is not None else None, out, mean, rstd,
+              first, plan.sel, plan.pos, 4, like=x)
         ctx.plan, ctx.first = plan, first
         ctx.save_for_backward(xn, mean, rstd, *ws, *bs, *mus)
         ctx.has_delta = delta is not None
@@ -849,12 +820,9 @@ class _AddLnMixRouted(torch.autograd.Function):
         dx = torch.empty_like(xn)
         dwb = torch.empty(2, 2, C, dtype=torch.float32, device=xn.device)
         dmu = torch.empty(2, C, dtype=torch.float32, device=xn.device)
-        lib = hip_lib.load()
-        ws = torch.empty(lib.vrwkv_ln_mix_routed_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
-        rc = lib.vrwkv_ln_mix_routed_bwd_bf16(ntok, T, C, xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr_array([w_t, w_v]), _ptr_array([b_t, b_v]),
-                                              _ptr_array([mu_t, mu_v]), dout.data_ptr(), _p(d_xn), _p(ctx.first), plan.sel.data_ptr(), plan.pos.data_ptr(), 4,
-                                              dx.data_ptr(), dwb.data_ptr(), dmu.data_ptr(), ws.data_ptr(), _stream(xn))
-        hip_lib.check(rc, "vrwkv_ln_mix_routed_bwd_bf16")
+        ws = torch.empty(hip_lib.load().vrwkv_ln_mix_routed_ws_floats(ntok, C), dtype=torch.float32, device=xn.device)
+        _glue("vrwkv_ln_mix_routed_bwd_bf16", ntok, T, C, xn, mean, rstd, [w_t, w_v], [b_t, b_v], [mu_t, mu_v], dout, d_xn, ctx.first, plan.sel, plan.pos, 4,
+              dx, dwb, dmu, ws, like=xn)
         dwb, dmus = _param_grads(dwb, dmu, w_t, xn, ctx.mu_shapes)
         return (dx, (dx if ctx.has_delta else None), dwb[0, 0], dwb[0, 1], dwb[1, 0], dwb[1, 1], None, None, None, *dmus)
 
@@ -865,8 +833,7 @@ def row_gather(src, idx):
     _chk(src)
     n, C = idx.numel(), src.shape[-1]
     out = torch.empty(n, C, dtype=src.dtype, device=src.device)
-    rc = hip_lib.load().vrwkv_row_gather_bf16(n, C, src.data_ptr(), idx.data_ptr(), idx.element_size(), out.data_ptr(), _stream(src))
-    hip_lib.check(rc, "vrwkv_row_gather_bf16")
+    _glue("vrwkv_row_gather_bf16", n, C, src, idx, idx.element_size(), out, like=src)
     return out
 
 
@@ -1064,9 +1031,7 @@ class _FusedCE(torch.autograd.Function):
         dev = logits.device
         row_loss, row_max, row_lse = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
         row_arg = torch.empty(n, dtype=torch.int32, device=dev)
-        rc = hip_lib.load().vrwkv_ce_fwd_bf16(n, V, logits.data_ptr(), labels.data_ptr(), row_loss.data_ptr(),
-                                              row_max.data_ptr(), row_lse.data_ptr(), row_arg.data_ptr(), _stream(logits))
-        hip_lib.check(rc, "vrwkv_ce_fwd_bf16")
+        _glue("vrwkv_ce_fwd_bf16", n, V, logits, labels, row_loss, row_max, row_lse, row_arg, like=logits)
         w = ((labels >= 0).float() / (valid.float().unsqueeze(1) * B)).view(n)      # d loss / d row_loss
         ctx.save_for_backward(logits, labels, w, row_max, row_lse, row_arg)
         return (row_loss * w).sum().to(logits.dtype)
@@ -1077,10 +1042,7 @@ class _FusedCE(torch.autograd.Function):
         B, T, V = logits.shape
         dlogits = torch.empty_like(logits)
         row_w = (w * g.float()).contiguous()
-        rc = hip_lib.load().vrwkv_ce_bwd_bf16(B * T, V, logits.data_ptr(), labels.data_ptr(), row_w.data_ptr(),
-                                              row_max.data_ptr(), row_lse.data_ptr(), row_arg.data_ptr(),
-                                              1e-4 / (B * T), dlogits.data_ptr(), _stream(logits))
-        hip_lib.check(rc, "vrwkv_ce_bwd_bf16")
+        _glue("vrwkv_ce_bwd_bf16", B * T, V, logits, labels, row_w, row_max, row_lse, row_arg, 1e-4 / (B * T), dlogits, like=logits)
         return dlogits, None, None
 
 
@@ -1205,9 +1167,7 @@ class _HeadCE(torch.autograd.Function):
         dev = x.device
         row_loss, row_max, row_lse = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
         row_arg = torch.empty(n, dtype=torch.int32, device=dev)
-        rc = hip_lib.load().vrwkv_ce_fwd_bf16(n, V, logits.data_ptr(), plan.labels.data_ptr(), row_loss.data_ptr(),
-                                              row_max.data_ptr(), row_lse.data_ptr(), row_arg.data_ptr(), _stream(logits))
-        hip_lib.check(rc, "vrwkv_ce_fwd_bf16")
+        _glue("vrwkv_ce_fwd_bf16", n, V, logits, plan.labels, row_loss, row_max, row_lse, row_arg, like=logits)
         ctx.save_for_backward(x, w, logits, row_max, row_lse, row_arg)
         ctx.plan = plan
         ctx.wparam = w if hasattr(w, "_vrwkv_flat_grad") else None
@@ -1221,8 +1181,6 @@ class _HeadCE(torch.autograd.Function):
         V = w.shape[0]
         N, n_real = B * Tp, B * plan.T
         dev = x.device
-        lib = hip_lib.load()
-        st = _stream(x)
         row_w = torch.zeros(B, Tp, dtype=torch.float32, device=dev)
         row_w[:, plan.pad:] = (plan.w * g.float()).view(B, plan.T)      # _FusedCE's row_w on the real rows, 0 on the pad rows
         row_w = row_w.view(N)
@@ -1238,17 +1196,13 @@ class _HeadCE(torch.autograd.Function):
             idx = torch.where(plan.pos >= -1, torch.arange(N, device=dev), -1)
         dlog = torch.empty(nrows, V, dtype=torch.bfloat16, device=dev)
         if nrows:
-            rc = lib.vrwkv_ce_bwd_rows_bf16(nrows, V, logits.data_ptr(), plan.labels.data_ptr(), row_w.data_ptr(), row_max.data_ptr(),
-                                            row_lse.data_ptr(), row_arg.data_ptr(), l2f, idx.data_ptr(), dlog.data_ptr(), st)
-            hip_lib.check(rc, "vrwkv_ce_bwd_rows_bf16")
+            _glue("vrwkv_ce_bwd_rows_bf16", nrows, V, logits, plan.labels, row_w, row_max, row_lse, row_arg, l2f, idx, dlog, like=x)
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dxc = F.linear(dlog, transpose2d(w)) if nrows else torch.empty(0, C, dtype=x.dtype, device=dev)
             if compact:
                 dx = torch.empty(N, C, dtype=x.dtype, device=dev)
-                rc = lib.vrwkv_head_dx_bf16(N, C, plan.pos.data_ptr(), dxc.data_ptr(), w.data_ptr(), row_max.data_ptr(), row_arg.data_ptr(),
-                                            l2f, dx.data_ptr(), st)
-                hip_lib.check(rc, "vrwkv_head_dx_bf16")
+                _glue("vrwkv_head_dx_bf16", N, C, plan.pos, dxc, w, row_max, row_arg, l2f, dx, like=x)
             else:
                 dx = dxc
             dx = dx.view(B, Tp, C)
@@ -1259,10 +1213,8 @@ class _HeadCE(torch.autograd.Function):
             if compact and n_u > 0:
                 key = torch.where(plan.pos == -1, row_arg.long(), V)
                 srow = torch.sort(key, stable=True).indices[:n_u].contiguous()
-                ws = torch.empty(lib.vrwkv_l2wrap_wgrad_ws_floats(n_u, C), dtype=torch.float32, device=dev)
-                rc = lib.vrwkv_l2wrap_wgrad_bf16(n_u, C, srow.data_ptr(), x2.data_ptr(), row_max.data_ptr(), row_arg.data_ptr(), l2f,
-                                                 dw.data_ptr(), ws.data_ptr(), st)
-                hip_lib.check(rc, "vrwkv_l2wrap_wgrad_bf16")
+                ws = torch.empty(hip_lib.load().vrwkv_l2wrap_wgrad_ws_floats(n_u, C), dtype=torch.float32, device=dev)
+                _glue("vrwkv_l2wrap_wgrad_bf16", n_u, C, srow, x2, row_max, row_arg, l2f, dw, ws, like=x)
         return dx, dw, None
 
 
@@ -1502,9 +1454,7 @@ def mix_prev(x, x_prev, *mus):
     mus_c = [m.reshape(C).contiguous() for m in mus]
     _chk(x, x_prev, *mus_c)
     outs = [torch.empty_like(x) for _ in mus]
-    rc = hip_lib.load().vrwkv_mix_fwd_prev_bf16(B * T, T, C, len(mus), x.data_ptr(), x_prev.data_ptr(), _ptr_array(mus_c),
-                                                _ptr_array(outs), _stream(x))
-    hip_lib.check(rc, "vrwkv_mix_fwd_prev_bf16")
+    _glue("vrwkv_mix_fwd_prev_bf16", B * T, T, C, len(mus), x, x_prev, mus_c, outs, like=x)
     return tuple(outs)
 
 
@@ -1572,8 +1522,7 @@ def adaptive_pool(image_features, side_out):
     if side * side != Ln:
         raise ValueError(f"{Ln} patch tokens are not a square grid")
     y = torch.empty(B, side_out * side_out, D, dtype=x.dtype, device=x.device)
-    hip_lib.check(hip_lib.load().vrwkv_adaptive_pool_bf16(B, side, side_out, D, x.data_ptr(), y.data_ptr(), _stream(x)),
-                  "vrwkv_adaptive_pool_bf16")
+    _glue("vrwkv_adaptive_pool_bf16", B, side, side_out, D, x, y, like=x)
     return y
 
 
@@ -1585,7 +1534,7 @@ class _Gate(torch.autograd.Function):
         x, g = x.contiguous(), g.contiguous()
         _chk(x, g)
         out = torch.empty_like(x)
-        hip_lib.check(hip_lib.load().vrwkv_gate_fwd_bf16(x.numel(), x.data_ptr(), g.data_ptr(), out.data_ptr(), _stream(x)), "vrwkv_gate_fwd_bf16")
+        _glue("vrwkv_gate_fwd_bf16", x.numel(), x, g, out, like=x)
         ctx.save_for_backward(x, g)
         return out
 
@@ -1595,8 +1544,7 @@ class _Gate(torch.autograd.Function):
         dout = dout.contiguous()
         dg = torch.empty_like(g)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        hip_lib.check(hip_lib.load().vrwkv_gate_bwd_bf16(x.numel(), x.data_ptr(), g.data_ptr(), dout.data_ptr(), dg.data_ptr(), _p(dx), _stream(x)),
-                      "vrwkv_gate_bwd_bf16")
+        _glue("vrwkv_gate_bwd_bf16", x.numel(), x, g, dout, dg, dx, like=x)
         return dx, dg
 
 
@@ -1610,7 +1558,7 @@ def gelu_(x, tanh_approx=False):
     _chk(x)
     if x.requires_grad or x.numel() % 8 != 0 or not x.is_contiguous():
         raise ValueError("gelu_: contiguous, no autograd, a multiple of 8 elements")
-    hip_lib.check(hip_lib.load().vrwkv_gelu_bf16(x.numel(), x.data_ptr(), x.data_ptr(), 1 if tanh_approx else 0, _stream(x)), "vrwkv_gelu_bf16")
+    _glue("vrwkv_gelu_bf16", x.numel(), x, x, 1 if tanh_approx else 0, like=x)
     return x
 
 
@@ -1625,8 +1573,7 @@ class _LnScatter(torch.autograd.Function):
         n, C = y.shape
         mean = torch.empty(n, dtype=torch.float32, device=y.device)
         rstd = torch.empty_like(mean)
-        hip_lib.check(hip_lib.load().vrwkv_ln_scatter_fwd_bf16(n, C, float(eps), y.data_ptr(), w.data_ptr(), b.data_ptr(), row_index.data_ptr(),
-                                                               embeds.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _stream(y)), "vrwkv_ln_scatter_fwd_bf16")
+        _glue("vrwkv_ln_scatter_fwd_bf16", n, C, float(eps), y, w, b, row_index, embeds, mean, rstd, like=y)
         ctx.mark_dirty(embeds)
         ctx.save_for_backward(y, w, mean, rstd, row_index)
         return embeds
@@ -1636,12 +1583,10 @@ class _LnScatter(torch.autograd.Function):
         y, w, mean, rstd, row_index = ctx.saved_tensors
         dout = dout.contiguous()
         n, C = y.shape
-        lib = hip_lib.load()
         dy = torch.empty_like(y)
         dwb = torch.empty(2, C, dtype=torch.float32, device=y.device)
-        ws = torch.empty(lib.vrwkv_add_ln_ws_floats(n, C), dtype=torch.float32, device=y.device)
-        hip_lib.check(lib.vrwkv_ln_gather_bwd_bf16(n, C, dout.data_ptr(), row_index.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                   w.data_ptr(), dy.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(y)), "vrwkv_ln_gather_bwd_bf16")
+        ws = torch.empty(hip_lib.load().vrwkv_add_ln_ws_floats(n, C), dtype=torch.float32, device=y.device)
+        _glue("vrwkv_ln_gather_bwd_bf16", n, C, dout, row_index, y, mean, rstd, w, dy, dwb, ws, like=y)
         d_emb = None
         if ctx.needs_input_grad[0]:                    # rows that were overwritten do not reach the embedding
             R = dout.shape[0]                          # dropped features carry row -1: they zero a scratch row past the end
@@ -1672,7 +1617,7 @@ class _FlipAdd(torch.autograd.Function):
         if delta is not None and delta.shape != x.shape:
             raise ValueError("flip_add: x and delta must have the same shape")
         out = torch.empty_like(x)
-        hip_lib.check(hip_lib.load().vrwkv_flip_add_bf16(B, T, C, x.data_ptr(), _p(delta), out.data_ptr(), _stream(x)), "vrwkv_flip_add_bf16")
+        _glue("vrwkv_flip_add_bf16", B, T, C, x, delta, out, like=x)
         ctx.has_delta = delta is not None
         return out
 
@@ -1682,7 +1627,7 @@ class _FlipAdd(torch.autograd.Function):
         dout = dout.contiguous()
         _chk(dout)
         dx = torch.empty_like(dout)
-        hip_lib.check(hip_lib.load().vrwkv_flip_add_bf16(B, T, C, dout.data_ptr(), 0, dx.data_ptr(), _stream(dout)), "vrwkv_flip_add_bf16")
+        _glue("vrwkv_flip_add_bf16", B, T, C, dout, None, dx, like=dout)
         return dx, (dx if ctx.has_delta else None)
 
 
@@ -1714,10 +1659,8 @@ class _LnPoolScatter(torch.autograd.Function):
         xn = torch.empty_like(x) if delta is not None else x
         mean = torch.empty(B * T, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
-        rc = hip_lib.load().vrwkv_ln_pool_scatter_fwd_bf16(B, T, int(pad), int(Lout), C, float(eps), x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(),
-                                                           _p(row_index), xn.data_ptr() if delta is not None else 0, out.data_ptr(), mean.data_ptr(),
-                                                           rstd.data_ptr(), _stream(x))
-        hip_lib.check(rc, "vrwkv_ln_pool_scatter_fwd_bf16")
+        _glue("vrwkv_ln_pool_scatter_fwd_bf16", B, T, int(pad), int(Lout), C, float(eps), x, delta, wc, bc, row_index, xn if delta is not None else None,
+              out, mean, rstd, like=x)
         if embeds is not None:
             ctx.mark_dirty(embeds)
         ctx.save_for_backward(xn, mean, rstd, wc, row_index)
@@ -1732,13 +1675,10 @@ class _LnPoolScatter(torch.autograd.Function):
         pad, Lout = ctx.geom
         dout = dout.contiguous()
         _chk(dout)
-        lib = hip_lib.load()
         dx = torch.empty_like(xn)
         dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
-        ws = torch.empty(lib.vrwkv_add_ln_ws_floats(B * T, C), dtype=torch.float32, device=xn.device)
-        rc = lib.vrwkv_ln_pool_gather_bwd_bf16(B, T, pad, Lout, C, dout.data_ptr(), _p(row_index), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                               wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
-        hip_lib.check(rc, "vrwkv_ln_pool_gather_bwd_bf16")
+        ws = torch.empty(hip_lib.load().vrwkv_add_ln_ws_floats(B * T, C), dtype=torch.float32, device=xn.device)
+        _glue("vrwkv_ln_pool_gather_bwd_bf16", B, T, pad, Lout, C, dout, row_index, xn, mean, rstd, wc, dx, dwb, ws, like=xn)
         d_emb = None
         if ctx.scatter and ctx.needs_input_grad[0]:    # as _LnScatter: rows that were overwritten do not reach the embedding
             R = dout.shape[0]
@@ -1887,10 +1827,7 @@ def patch_embed(x, weight, bias, pos=None, prefix=None, padded_weight=None):
     wp = padded_weight if padded_weight is not None else padded_patch_weight(weight)
     bias = None if bias is None else bias.detach().to(torch.bfloat16).contiguous()
     pos = None if pos is None else pos.detach().to(torch.bfloat16).reshape(M, N).contiguous()
-    rc = hip_lib.load().vrwkv_patch_embed_bf16(B, H, W, patch, N, _p(x), _p(wp), None if bias is None else _p(bias),
-                                               None if pos is None else _p(pos), _p(out), npre + M, npre,
-                                               hip_lib.launch_stream(x.device))
-    hip_lib.check(rc, "vrwkv_patch_embed_bf16")
+    _glue("vrwkv_patch_embed_bf16", B, H, W, patch, N, x, wp, bias, pos, out, npre + M, npre, like=x)
     return out
 
 
@@ -1941,12 +1878,10 @@ class _PatchEmbedTrain(torch.autograd.Function):
             cols = F.unfold(x, patch, stride=patch).transpose(1, 2).reshape(d2.shape[0], -1)
             dw = wgrad_big(d2, cols) if wgrad_big_supported(d2, cols) else d2.t() @ cols
             return None, dw.view(ctx.wshape), (d2.sum(0, dtype=torch.float32).to(d2.dtype) if ctx.has_bias else None)
-        lib = hip_lib.load()
         dw = torch.empty(ctx.wshape, dtype=torch.bfloat16, device=x.device)
         db = torch.empty(N, dtype=torch.bfloat16, device=x.device) if ctx.has_bias else None
-        ws = torch.empty(lib.vrwkv_patch_embed_wgrad_ws_floats(B, H, W, patch, N), dtype=torch.float32, device=x.device)
-        rc = lib.vrwkv_patch_embed_wgrad_bf16(B, H, W, patch, N, x.data_ptr(), d2.data_ptr(), dw.data_ptr(), _p(db), ws.data_ptr(), _stream(x))
-        hip_lib.check(rc, "vrwkv_patch_embed_wgrad_bf16")
+        ws = torch.empty(hip_lib.load().vrwkv_patch_embed_wgrad_ws_floats(B, H, W, patch, N), dtype=torch.float32, device=x.device)
+        _glue("vrwkv_patch_embed_wgrad_bf16", B, H, W, patch, N, x, d2, dw, db, ws, like=x)
         return None, dw, db
 
 
@@ -1975,17 +1910,14 @@ class _LnScatterMean(torch.autograd.Function):
             raise ValueError(f"ln_scatter_mean: row_index must hold {B * L} contiguous int64 rows on {x.device}")
         if embeds is not None and (embeds.dim() != 2 or embeds.shape[1] != C or not embeds.is_contiguous()):
             raise ValueError("ln_scatter_mean: embeds must be a contiguous (rows, C) tensor")
-        lib = hip_lib.load()
         out = embeds if embeds is not None else torch.empty(B * L, C, dtype=x.dtype, device=x.device)
         pooled = torch.empty(B, C, dtype=x.dtype, device=x.device)
         xn = torch.empty_like(x) if delta is not None else x
         mean = torch.empty(B * L, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
-        ws = torch.empty(lib.vrwkv_ln_scatter_mean_ws_floats(B, L, C), dtype=torch.float32, device=x.device)
-        rc = lib.vrwkv_ln_scatter_mean_fwd_bf16(B, L, C, float(eps), x.data_ptr(), _p(delta), wc.data_ptr(), bc.data_ptr(), _p(row_index),
-                                                xn.data_ptr() if delta is not None else 0, out.data_ptr(), pooled.data_ptr(), mean.data_ptr(),
-                                                rstd.data_ptr(), ws.data_ptr(), _stream(x))
-        hip_lib.check(rc, "vrwkv_ln_scatter_mean_fwd_bf16")
+        ws = torch.empty(hip_lib.load().vrwkv_ln_scatter_mean_ws_floats(B, L, C), dtype=torch.float32, device=x.device)
+        _glue("vrwkv_ln_scatter_mean_fwd_bf16", B, L, C, float(eps), x, delta, wc, bc, row_index, xn if delta is not None else None, out, pooled, mean,
+              rstd, ws, like=x)
         if embeds is not None:
             ctx.mark_dirty(embeds)
         ctx.set_materialize_grads(False)
@@ -2002,13 +1934,10 @@ class _LnScatterMean(torch.autograd.Function):
         dout = dout.contiguous() if dout is not None else None
         dpooled = dpooled.contiguous() if dpooled is not None else None
         _chk(dout, dpooled)
-        lib = hip_lib.load()
         dx = torch.empty_like(xn)
         dwb = torch.empty(2, C, dtype=torch.float32, device=xn.device)
-        ws = torch.empty(lib.vrwkv_ln_scatter_mean_ws_floats(B, L, C), dtype=torch.float32, device=xn.device)
-        rc = lib.vrwkv_ln_gather_mean_bwd_bf16(B, L, C, _p(dout), _p(row_index), _p(dpooled), xn.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                               wc.data_ptr(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), _stream(xn))
-        hip_lib.check(rc, "vrwkv_ln_gather_mean_bwd_bf16")
+        ws = torch.empty(hip_lib.load().vrwkv_ln_scatter_mean_ws_floats(B, L, C), dtype=torch.float32, device=xn.device)
+        _glue("vrwkv_ln_gather_mean_bwd_bf16", B, L, C, dout, row_index, dpooled, xn, mean, rstd, wc, dx, dwb, ws, like=xn)
         d_emb = None
         if ctx.scatter and ctx.needs_input_grad[0] and dout is not None:    # as _LnScatter: rows that were overwritten do not reach the embedding
             R = dout.shape[0]

@@ -22,9 +22,7 @@ def flash_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Te
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     o = torch.empty(B, L, H, D, dtype=q.dtype, device=q.device)
     sb, sl, sh, _ = q.stride()
-    rc = hip_lib.load().vrwkv_attention_fwd_bf16(B, L, H, D, q.data_ptr(), k.data_ptr(), v.data_ptr(), sb, sl, sh,
-                                                 o.data_ptr(), hip_lib.launch_stream(q.device))
-    hip_lib.check(rc, "vrwkv_attention_fwd_bf16")
+    hip_lib.launch("vrwkv_attention_fwd_bf16", B, L, H, D, q, k, v, sb, sl, sh, o, device=q.device)
     return o
 
 
@@ -53,8 +51,5 @@ def flash_forward_relpos(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_
     rel_w = rel_w.to(torch.bfloat16).contiguous()
     o = torch.empty(B, L, H, D, dtype=q.dtype, device=q.device)
     sb, sl, sh, _ = q.stride()
-    rc = hip_lib.load().vrwkv_attention_relpos_fwd_bf16(B, side, H, D, q.data_ptr(), k.data_ptr(), v.data_ptr(), sb, sl, sh,
-                                                        rel_h.data_ptr(), rel_w.data_ptr(), o.data_ptr(),
-                                                        hip_lib.launch_stream(q.device))
-    hip_lib.check(rc, "vrwkv_attention_relpos_fwd_bf16")
+    hip_lib.launch("vrwkv_attention_relpos_fwd_bf16", B, side, H, D, q, k, v, sb, sl, sh, rel_h, rel_w, o, device=q.device)
     return o

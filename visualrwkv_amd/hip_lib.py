@@ -208,11 +208,6 @@ def check(code: int, what: str) -> None:
         raise RuntimeError(f"{what} failed: {msg} (code {code})")
 
 
-def p(t) -> int:
-    """A tensor's address, NULL for None."""
-    return t.data_ptr() if t is not None else 0
-
-
 class _ArrayTypes(dict):
     """ctypes array types of one element type by length, made once."""
     def __init__(self, ctype):
@@ -237,10 +232,12 @@ def array(vs):
 _Tensor = _Parameter = None
 
 
-def launch(name: str, *args, device) -> None:
-    """One launch of the library entry `name` on PyTorch's current stream of `device`: the one way the wrappers call an entry.  The entry gets
-    `args` -- tensors as pointers, None as NULL, lists as C arrays (array()), numbers as they are -- then the stream; a code other than 0 raises
-    (check)."""
+def launch(name: str, *args, device, allow=()) -> int:
+    """One launch of the library entry `name` on PyTorch's current stream of `device`: how every wrapper of the package launches.  The entry gets
+    `args` -- tensors as pointers, None as NULL, lists and tuples as C arrays (array()), numbers and anything else (a ctypes array) as they are --
+    then the stream.  Returns the entry's code, which is 0 or one of `allow`; any other code raises (check).  Nothing about a tensor is checked
+    here: dtype, layout and device are the caller's, in front of the call.  What is not a launch -- size queries, setters, the host entries,
+    which take no stream -- is called on load() / load_host() directly."""
     global _Tensor, _Parameter
     if _Tensor is None:
         from torch import Tensor as _Tensor
@@ -250,7 +247,25 @@ def launch(name: str, *args, device) -> None:
     # the common case first and by exact type -- a tensor or a parameter -- then lists; isinstance only for what is left (tensor subclasses, numbers).
     conv = [a.data_ptr() if (t := type(a)) is Tensor or t is Parameter else array(a) if t is list or t is tuple else 0 if a is None
             else a.data_ptr() if isinstance(a, Tensor) else a for a in args]
-    check(getattr(load(), name)(*conv, launch_stream(device)), name)
+    rc = getattr(load(), name)(*conv, launch_stream(device))
+    if rc != 0 and rc not in allow:
+        check(rc, name)
+    return rc
+
+
+def timed(log, kind, elems, device, fn):
+    """fn() -- with `log` a list, between two HIP events on PyTorch's current stream of `device`, appended as (kind, start, end, elems): the
+    per-launch timing behind wkv7.EVENT_LOG and wkv6.EVENT_LOG."""
+    if log is None:
+        return fn()
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    st = torch.cuda.current_stream(device)
+    e0.record(st)
+    rc = fn()
+    e1.record(st)
+    log.append((kind, e0, e1, elems))
+    return rc
 
 
 def launch_stream(device) -> int:

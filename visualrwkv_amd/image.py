@@ -27,9 +27,7 @@ def _hip_resize_normalize(img_u8: torch.Tensor, size: int, mean, std, dtype) -> 
     H, W, _ = img.shape
     out = torch.empty(1, 3, size, size, dtype=dtype, device=img.device)
     m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-    rc = hip_lib.load().vrwkv_resize_normalize_u8(H, W, img.data_ptr(), size, m3, s3, out.data_ptr(), int(dtype == torch.float32),
-                                                  hip_lib.launch_stream(img.device))
-    hip_lib.check(rc, "vrwkv_resize_normalize_u8")
+    hip_lib.launch("vrwkv_resize_normalize_u8", H, W, img, size, m3, s3, out, int(dtype == torch.float32), device=img.device)
     return out
 
 

@@ -37,10 +37,6 @@ def _chk(name, t, shape, dtype):
                          f"got {t.dtype} {tuple(t.shape)} contiguous={t.is_contiguous()}")
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def ckpt_tensor(B, T, H, device):
     n = hip_lib.load().vrwkv_wkv6_ckpt_floats(B, T, H)
     return torch.empty(n, dtype=torch.float32, device=device)
@@ -51,22 +47,16 @@ def ckpt_tensor(B, T, H, device):
 EVENT_LOG = None
 
 
-def _timed(kind, elems, dev, fn):
-    if EVENT_LOG is None:
-        return fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    st = torch.cuda.current_stream(dev)
-    e0.record(st)
-    rc = fn()
-    e1.record(st)
-    EVENT_LOG.append((kind, e0, e1, elems))
-    return rc
+def _launch(name, kind, B, T, C, H, r, *args):
+    """One launch of the state entry `name` on r's device (hip_lib.launch), logged in EVENT_LOG as `kind`."""
+    with torch.cuda.device(r.device):               # the op surface accepts tensors of any device; hip_lib.launch wants theirs current
+        hip_lib.timed(EVENT_LOG, kind, B * T * C, r.device, lambda: hip_lib.launch(name, B, T, C, H, r, *args, device=r.device))
 
 
 def _chk_state(name, t, B, H):
     if t is not None:
         _chk(name, t, (B, H, HEAD_SIZE, HEAD_SIZE), torch.float32)
-    return t.data_ptr() if t is not None else 0
+    return t
 
 
 def forward_hip(B, T, C, H, r, k, v, ew, u, y, ckpt=None, state0=None, state_T=None):
@@ -80,11 +70,7 @@ def forward_hip(B, T, C, H, r, k, v, ew, u, y, ckpt=None, state0=None, state_T=N
         raise ValueError(f"wkv6: u must have {C} elements")
     _chk("u", u, u.shape, bf)
     s0, sT = _chk_state("state0", state0, B, H), _chk_state("state_T", state_T, B, H)
-    with torch.cuda.device(r.device):
-        rc = _timed("fwd", B * T * C, r.device, lambda: hip_lib.load().vrwkv_wkv6_forward_state_bf16(
-            B, T, C, H, r.data_ptr(), k.data_ptr(), v.data_ptr(), ew.data_ptr(), u.data_ptr(), s0, y.data_ptr(), sT,
-            ckpt.data_ptr() if ckpt is not None else 0, _stream(r)))
-    hip_lib.check(rc, "vrwkv_wkv6_forward_state_bf16")
+    _launch("vrwkv_wkv6_forward_state_bf16", "fwd", B, T, C, H, r, k, v, ew, u, s0, y, sT, ckpt)
 
 
 def backward_hip(B, T, C, H, r, k, v, ew, u, gy, gr, gk, gv, gw, gu, ckpt=None, state0=None, d_state_T=None, d_state0=None):
@@ -100,11 +86,7 @@ def backward_hip(B, T, C, H, r, k, v, ew, u, gy, gr, gk, gv, gw, gu, ckpt=None, 
         ckpt = ckpt_tensor(B, T, H, r.device)
         forward_hip(B, T, C, H, r, k, v, ew, u, torch.empty_like(r), ckpt, state0)
     dT, d0 = _chk_state("d_state_T", d_state_T, B, H), _chk_state("d_state0", d_state0, B, H)
-    with torch.cuda.device(r.device):
-        rc = _timed("bwd", B * T * C, r.device, lambda: hip_lib.load().vrwkv_wkv6_backward_state_bf16(
-            B, T, C, H, r.data_ptr(), k.data_ptr(), v.data_ptr(), ew.data_ptr(), u.data_ptr(), gy.data_ptr(), ckpt.data_ptr(), dT, gr.data_ptr(),
-            gk.data_ptr(), gv.data_ptr(), gw.data_ptr(), gu.data_ptr(), d0, _stream(r)))
-    hip_lib.check(rc, "vrwkv_wkv6_backward_state_bf16")
+    _launch("vrwkv_wkv6_backward_state_bf16", "bwd", B, T, C, H, r, k, v, ew, u, gy, ckpt, dT, gr, gk, gv, gw, gu, d0)
 
 
 def _apply_variant_env():

@@ -44,31 +44,13 @@ _TPAR_ENV = os.environ.get("VRWKV_TPAR_BWD", "auto")
 TPARALLEL_BWD = _TPAR_ENV != "0"
 
 
-def _timed(kind, elems, stream_dev, fn):
-    if EVENT_LOG is None:
-        return fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    st = torch.cuda.current_stream(stream_dev)
-    e0.record(st)
-    rc = fn()
-    e1.record(st)
-    EVENT_LOG.append((kind, e0, e1, elems))
-    return rc
-
-
 def _call(name, kind, w, *args, allow=()):
-    """One launch of the library entry `name` on w's device and PyTorch's current stream there.  The entry gets w's leading sizes ((B, T, H);
-    (B, H) for the step), then `args` -- tensors as pointers, None as NULL, numbers as they are -- then the stream.  kind: the EVENT_LOG key
-    (None: the launch is not logged).  Returns the entry's code, which is 0 or one of `allow`: anything else raises (hip_lib.check)."""
-    fn = getattr(hip_lib.load(), name)
-    ptrs = [0 if x is None else x.data_ptr() if isinstance(x, torch.Tensor) else x for x in args]
-    with torch.cuda.device(w.device):
-        stream = torch.cuda.current_stream(w.device).cuda_stream
-        launch = lambda: fn(*w.shape[:-1], *ptrs, stream)
-        rc = launch() if kind is None else _timed(kind, w.numel(), w.device, launch)
-    if rc not in allow:
-        hip_lib.check(rc, name)
-    return rc
+    """One launch of the library entry `name` on w's device and PyTorch's current stream there (hip_lib.launch).  The entry gets w's leading
+    sizes ((B, T, H); (B, H) for the step), then `args`, then the stream.  kind: the EVENT_LOG key (None: the launch is not logged).  Returns
+    the entry's code, which is 0 or one of `allow`: anything else raises."""
+    with torch.cuda.device(w.device):               # the op surface accepts tensors of any device; hip_lib.launch wants theirs current
+        launch = lambda: hip_lib.launch(name, *w.shape[:-1], *args, device=w.device, allow=allow)
+        return launch() if kind is None else hip_lib.timed(EVENT_LOG, kind, w.numel(), w.device, launch)
 
 
 def _byproducts(w):
