@@ -1,6 +1,8 @@
-// Tower image transform under the host emulator.  TEST INFRASTRUCTURE ONLY.
+// Tower image transform under the host emulator: csrc/image_ops.hip whole (kernel header, launcher and C entry point; the kernel is no template,
+// so one unit holds both) and a direct launch of the kernel.  TEST INFRASTRUCTURE ONLY.
+#include <hip/hip_runtime.h>
 #include <gfx950_prims.h>
-#include <image_kernels.h>
+#include "../../visualrwkv_amd/csrc/image_ops.hip"
 
 extern "C" int emu_resize_normalize_u8(int H, int W, const void* src, int S, const float* mean3, const float* std3, void* dst, int f32) {
     vimg::Args a{};

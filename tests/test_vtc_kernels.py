@@ -49,7 +49,7 @@ from tests.shape_checks import Checks
 from tests.test_glue_shapes import F32, I, L, P, VP, bits, f64, nan_rows, rnd, same_bits, written
 from tests.test_ln_shapes import EPS, FLIP, LN_BWD_GRID, PERR, TOL, LnBackend, nan_ws, ref_ln, ste
 
-EINVAL, ESHAPE = -1, -2
+EINVAL, ESHAPE, EALIGN = -1, -2, -3
 BACKENDS = ["emu", pytest.param("hip", marks=pytest.mark.gpu)]
 FLIP_GRID_THREADS = 2048 * 256                 # fused_ops.hip: grid_for's cap x the workgroup size
 
@@ -121,6 +121,10 @@ def test_flip_add_arguments(backend, be):
     assert rc(a5=P(x[1:])) == EINVAL and rc(a3=P(out[1:]), a4=None) == EINVAL, "out overlaps an input"
     assert rc(a0=0) == EINVAL and rc(a1=0) == EINVAL and rc(a3=None) == EINVAL and rc(a5=None) == EINVAL
     assert rc(a2=60) == ESHAPE and rc(a2=0) == ESHAPE
+    for k, t in (("a3", x), ("a4", d), ("a5", out)):
+        assert rc(**{k: VP(t.data_ptr() + 8)}) == EALIGN, (k, "8 bytes off a 16-byte boundary")
+    assert rc(a5=VP(x.data_ptr() + 8)) == EINVAL and rc(a3=VP(out.data_ptr() + 8), a4=None) == EINVAL, "the overlap is found before the alignment"
+    assert rc(a2=60, a3=VP(x.data_ptr() + 8)) == ESHAPE and rc(a3=None, a5=VP(out.data_ptr() + 8)) == EINVAL
     assert torch.equal(bits(x), bits(x0)) and torch.equal(bits(d), bits(d0)) and bool(torch.isnan(out.float()).all()), "a refused call wrote"
     assert rc() == 0 and rc(a4=None) == 0
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <attention_kernels.h>
+#include <host_checks.h>
 
 namespace {
 
@@ -15,12 +16,7 @@ int launch(const vattn::Args& a, int B, hipStream_t stream) {
     vattn::Args p = a;
     p.nqb = (a.L + G::NQ - 1) / G::NQ;
     p.BH = B * a.H;
-    auto kern = vattn::fwd_kernel<D, QT, S>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(p.nqb * p.BH)), dim3(256), G::LDS_BYTES, stream, p);
-    e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return hostchk::launch_lds(vattn::fwd_kernel<D, QT, S>, dim3((unsigned)(p.nqb * p.BH)), dim3(256), G::LDS_BYTES, stream, p);
 }
 
 template <int D, int S>
@@ -30,10 +26,9 @@ int launch_qt(const vattn::Args& a, int B, hipStream_t stream) {
 }
 
 int check(int B, int L, int H, const void* q, const void* k, const void* v, const void* o, long sb, long sl, long sh) {
-    if (B <= 0 || L <= 0 || H <= 0 || !q || !k || !v || !o) return VRWKV_EINVAL;
+    if (B <= 0 || L <= 0 || H <= 0 || hostchk::any_null(q, k, v, o)) return VRWKV_EINVAL;
     if ((sb | sl | sh) % 8 != 0) return VRWKV_EALIGN;       // 16-byte rows
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-         reinterpret_cast<uintptr_t>(o)) & 15u) return VRWKV_EALIGN;
+    if (hostchk::any_misaligned(q, k, v, o)) return VRWKV_EALIGN;
     return VRWKV_OK;
 }
 
@@ -60,8 +55,8 @@ extern "C" int vrwkv_attention_relpos_fwd_bf16(int B, int S, int H, int D, const
                                                const void* rel_w, void* o, void* stream) {
     const int L = S * S;
     if (int rc = check(B, L, H, q, k, v, o, stride_b, stride_l, stride_h)) return rc;
-    if (!rel_h || !rel_w) return VRWKV_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(rel_h) | reinterpret_cast<uintptr_t>(rel_w)) & 15u) return VRWKV_EALIGN;
+    if (hostchk::any_null(rel_h, rel_w)) return VRWKV_EINVAL;
+    if (hostchk::any_misaligned(rel_h, rel_w)) return VRWKV_EALIGN;
     if (D != 64 || (S != 14 && S != 64)) return VRWKV_ESHAPE;
     vattn::Args p{(const uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v, (uint16_t*)o, stride_b, stride_l, stride_h, L, H,
                   (float)(1.4426950408889634 / sqrt((double)D)), (const uint16_t*)rel_h, (const uint16_t*)rel_w, 0, 0};

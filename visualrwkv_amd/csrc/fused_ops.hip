@@ -5,6 +5,9 @@
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
+#include <host_checks.h>
+
+using hostchk::any_misaligned, hostchk::any_null, hostchk::finish_launch, hostchk::grid_for;
 
 namespace {
 
@@ -71,11 +74,6 @@ __global__ __launch_bounds__(256) void sqnorm_bf16_kernel(long n, const uint16_t
     if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
 }
 
-int grid_for(long nvec) {
-    long b = (nvec + 255) / 256;
-    return (int)(b < 1 ? 1 : b > 2048 ? 2048 : b);      // <= 8 workgroups per CU, grid-stride the rest
-}
-
 // out[b, T-1-t, :] = bf16(x[b, t, :] + delta[b, t, :]) (VisualTokenCompressor.forward's x.flip(1), VisualRWKV-v7/v7.04/src/model.py:359-370, with the
 // residual add that the Block before left pending); delta == nullptr: the pure flip.  cv = C / 8 16-byte pieces per row; a row stays contiguous, so
 // reads and writes are both whole 16-byte pieces in row order.  Each piece is read once and never again here: non-temporal both ways.
@@ -95,6 +93,19 @@ __global__ __launch_bounds__(256) void flip_add_kernel(long nvec, int T, int cv,
     }
 }
 
+// Both AdamW entries.  sqnorm (may be NULL): the clip factor is formed on the device from it and `clip`, and `scale` is 1 / world; without it `scale`
+// is the whole gradient scale.
+int adamw(long n, float* master, float* m, float* v, const void* grad, void* param, float lr, float beta1, float beta2, float eps, float weight_decay,
+          int step, const float* sqnorm, float scale, float clip, long global_offset, long wd_boundary, void* stream) {
+    if (n <= 0 || any_null(master, m, v, grad, param) || step < 1) return VRWKV_EINVAL;
+    if (n % 4 != 0) return VRWKV_ESHAPE;
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)(((n >> 2) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, master, m, v,
+                       (const uint16_t*)grad, (uint16_t*)param, lr, beta1, beta2, eps, weight_decay,
+                       (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), scale, global_offset, wd_boundary, sqnorm, clip);
+    return finish_launch();
+}
+
 }  // namespace
 
 extern "C" {
@@ -102,40 +113,26 @@ extern "C" {
 int vrwkv_adamw_step_bf16(long n, float* master, float* m, float* v, const void* grad, void* param,
                           float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                           float grad_scale, long global_offset, long wd_boundary, void* stream) {
-    if (n <= 0 || !master || !m || !v || !grad || !param || step < 1) return VRWKV_EINVAL;
-    if (n % 4 != 0) return VRWKV_ESHAPE;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)(((n >> 2) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, master, m, v,
-                       (const uint16_t*)grad, (uint16_t*)param, lr, beta1, beta2, eps, weight_decay,
-                       (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), grad_scale, global_offset, wd_boundary, (const float*)nullptr, 0.f);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return adamw(n, master, m, v, grad, param, lr, beta1, beta2, eps, weight_decay, step, nullptr, grad_scale, 0.f, global_offset, wd_boundary, stream);
 }
 
 int vrwkv_adamw_step_clip_bf16(long n, float* master, float* m, float* v, const void* grad, void* param,
                                float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                const float* sqnorm, float inv_world, float clip, long global_offset, long wd_boundary,
                                void* stream) {
-    if (n <= 0 || !master || !m || !v || !grad || !param || !sqnorm || step < 1) return VRWKV_EINVAL;
-    if (n % 4 != 0) return VRWKV_ESHAPE;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)(((n >> 2) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, master, m, v,
-                       (const uint16_t*)grad, (uint16_t*)param, lr, beta1, beta2, eps, weight_decay,
-                       (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), inv_world, global_offset, wd_boundary, sqnorm, clip);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    if (!sqnorm) return VRWKV_EINVAL;
+    return adamw(n, master, m, v, grad, param, lr, beta1, beta2, eps, weight_decay, step, sqnorm, inv_world, clip, global_offset, wd_boundary, stream);
 }
 
 int vrwkv_sqnorm_bf16(long n, const void* x, float* out, void* stream) {
-    if (n <= 0 || !x || !out) return VRWKV_EINVAL;
+    if (n <= 0 || any_null(x, out)) return VRWKV_EINVAL;
     if (n % 8 != 0) return VRWKV_ESHAPE;
     hipLaunchKernelGGL(sqnorm_bf16_kernel, dim3(grid_for(n >> 3)), dim3(256), 0, (hipStream_t)stream, n, (const uint16_t*)x, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 int vrwkv_flip_add_bf16(int B, int T, int C, const void* x, const void* delta, void* out, void* stream) {
-    if (B <= 0 || T <= 0 || !x || !out) return VRWKV_EINVAL;
+    if (B <= 0 || T <= 0 || any_null(x, out)) return VRWKV_EINVAL;
     if (C <= 0 || C % 8 != 0) return VRWKV_ESHAPE;
     const size_t bytes = (size_t)B * T * C * 2;
     const uintptr_t o = reinterpret_cast<uintptr_t>(out);
@@ -144,12 +141,11 @@ int vrwkv_flip_add_bf16(int B, int T, int C, const void* x, const void* delta, v
         const uintptr_t a = reinterpret_cast<uintptr_t>(in);
         if (in && o < a + bytes && a < o + bytes) return VRWKV_EINVAL;
     }
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(delta) | o) & 15u) return VRWKV_EALIGN;
+    if (any_misaligned(x, delta, out)) return VRWKV_EALIGN;
     const long nvec = (long)B * T * (C / 8);
     hipLaunchKernelGGL(flip_add_kernel, dim3(grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, nvec, T, C / 8, (const uint16_t*)x,
                        (const uint16_t*)delta, (uint16_t*)out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 }  // extern "C"
@@ -183,11 +179,10 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(int rows, int cols,
 }  // namespace
 
 extern "C" int vrwkv_transpose_bf16(long rows, long cols, const void* in, void* out, void* stream) {
-    if (rows <= 0 || cols <= 0 || !in || !out) return VRWKV_EINVAL;
+    if (rows <= 0 || cols <= 0 || any_null(in, out)) return VRWKV_EINVAL;
     if (rows % 64 || cols % 64 || rows > 0x7fffffffL || cols > 0x7fffffffL) return VRWKV_ESHAPE;
-    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return VRWKV_EALIGN;
+    if (any_misaligned(in, out)) return VRWKV_EALIGN;
     hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)(cols / 64), (unsigned)(rows / 64)), dim3(256), 0, (hipStream_t)stream,
                        (int)rows, (int)cols, (const uint16_t*)in, (uint16_t*)out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }

@@ -13,6 +13,9 @@
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
+#include <host_checks.h>
+
+using hostchk::any_null, hostchk::finish_launch;
 
 namespace {
 
@@ -244,42 +247,38 @@ extern "C" {
 
 int vrwkv_ce_fwd_bf16(long nrows, int V, const void* logits, const long* labels, float* row_loss, float* row_max,
                       float* row_lse, int* row_argmax, void* stream) {
-    if (nrows <= 0 || !logits || !labels || !row_loss || !row_max || !row_lse || !row_argmax) return VRWKV_EINVAL;
+    if (nrows <= 0 || any_null(logits, labels, row_loss, row_max, row_lse, row_argmax)) return VRWKV_EINVAL;
     if (V <= 0 || V % 8 != 0) return VRWKV_ESHAPE;
     hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)nrows), dim3(CE_THREADS), 0, (hipStream_t)stream, V,
                        (const uint16_t*)logits, labels, row_loss, row_max, row_lse, row_argmax);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 int vrwkv_ce_bwd_bf16(long nrows, int V, const void* logits, const long* labels, const float* row_w, const float* row_max,
                       const float* row_lse, const int* row_argmax, float l2_factor, void* dlogits, void* stream) {
-    if (nrows <= 0 || !logits || !labels || !row_w || !row_max || !row_lse || !row_argmax || !dlogits) return VRWKV_EINVAL;
+    if (nrows <= 0 || any_null(logits, labels, row_w, row_max, row_lse, row_argmax, dlogits)) return VRWKV_EINVAL;
     if (V <= 0 || V % 8 != 0) return VRWKV_ESHAPE;
     hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)nrows), dim3(CE_THREADS), 0, (hipStream_t)stream, V,
                        (const uint16_t*)logits, labels, row_w, row_max, row_lse, row_argmax, l2_factor, (uint16_t*)dlogits);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 int vrwkv_ce_bwd_rows_bf16(long nrows, int V, const void* logits, const long* labels, const float* row_w, const float* row_max,
                            const float* row_lse, const int* row_argmax, float l2_factor, const long* idx, void* dlogits, void* stream) {
-    if (nrows <= 0 || !logits || !labels || !row_w || !row_max || !row_lse || !row_argmax || !idx || !dlogits) return VRWKV_EINVAL;
+    if (nrows <= 0 || any_null(logits, labels, row_w, row_max, row_lse, row_argmax, idx, dlogits)) return VRWKV_EINVAL;
     if (V <= 0 || V % 8 != 0) return VRWKV_ESHAPE;
     hipLaunchKernelGGL(ce_bwd_rows_kernel, dim3((unsigned)nrows), dim3(CE_THREADS), 0, (hipStream_t)stream, V, (const uint16_t*)logits,
                        labels, row_w, row_max, row_lse, row_argmax, l2_factor, idx, (uint16_t*)dlogits);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 int vrwkv_head_dx_bf16(long nrows, int C, const long* pos, const void* dxc, const void* W, const float* row_max, const int* row_argmax,
                        float l2_factor, void* dx, void* stream) {
-    if (nrows <= 0 || !pos || !W || !row_max || !row_argmax || !dx) return VRWKV_EINVAL;     // dxc: NULL when no row has pos >= 0
+    if (nrows <= 0 || any_null(pos, W, row_max, row_argmax, dx)) return VRWKV_EINVAL;     // dxc: NULL when no row has pos >= 0
     if (C <= 0 || C % 8 != 0) return VRWKV_ESHAPE;
     hipLaunchKernelGGL(head_dx_kernel, dim3((unsigned)nrows), dim3(CE_THREADS), 0, (hipStream_t)stream, C, pos, (const uint16_t*)dxc,
                        (const uint16_t*)W, row_max, row_argmax, l2_factor, (uint16_t*)dx);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 long vrwkv_l2wrap_wgrad_ws_floats(long n, int C) {
@@ -289,7 +288,7 @@ long vrwkv_l2wrap_wgrad_ws_floats(long n, int C) {
 
 int vrwkv_l2wrap_wgrad_bf16(long n, int C, const long* srow, const void* x, const float* row_max, const int* row_argmax, float l2_factor,
                             void* dW, float* ws, void* stream) {
-    if (n < 0 || !srow || !x || !row_max || !row_argmax || !dW || !ws) return VRWKV_EINVAL;
+    if (n < 0 || any_null(srow, x, row_max, row_argmax, dW, ws)) return VRWKV_EINVAL;
     if (C <= 0 || C % 8 != 0) return VRWKV_ESHAPE;
     if (n == 0) return VRWKV_OK;
     const long tiles = (n + L2W_TILE - 1) / L2W_TILE;
@@ -298,12 +297,10 @@ int vrwkv_l2wrap_wgrad_bf16(long n, int C, const long* srow, const void* x, cons
     const dim3 grid((unsigned)tiles, (unsigned)((C / 8 + L2W_THREADS - 1) / L2W_THREADS));
     hipLaunchKernelGGL(l2wrap_wgrad_tiles, grid, dim3(L2W_THREADS), 0, (hipStream_t)stream, n, C, srow, (const uint16_t*)x, row_max,
                        row_argmax, l2_factor, (uint16_t*)dW, P, Q);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (int rc = finish_launch()) return rc;
     hipLaunchKernelGGL(l2wrap_wgrad_join, grid, dim3(L2W_THREADS), 0, (hipStream_t)stream, n, C, srow, row_argmax, (uint16_t*)dW,
                        (const float*)P, (const float*)Q);
-    e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 }  // extern "C"

@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
+#include <host_checks.h>
+
+using hostchk::any_misaligned, hostchk::any_null, hostchk::finish_launch;
 
 namespace {
 
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(256) void stream_mix_kernel(const u32x4_t* __restri
 
 // bytes = size of ONE array; returns 0 / error.  a, b: sources; d0, d1: destinations (unused ones may alias).
 extern "C" int vrwkv_stream_probe(int mode, const void* a, const void* b, void* d0, void* d1, long bytes, void* stream) {
-    if (!a || !d0 || bytes <= 0 || bytes % 16 != 0) return VRWKV_EINVAL;
+    if (any_null(a, d0) || bytes <= 0 || bytes % 16 != 0) return VRWKV_EINVAL;
     const dim3 grid(256 * 8), block(256);
     const long nvec = bytes / 16;
     hipStream_t st = (hipStream_t)stream;
@@ -186,21 +189,19 @@ extern "C" int vrwkv_stream_probe(int mode, const void* a, const void* b, void* 
         case 4: hipLaunchKernelGGL(stream_mix_kernel<4>, grid, block, 0, st, (const u32x4_t*)a, (const u32x4_t*)b, (u32x4_t*)d0, (u32x4_t*)d1, nvec); break;
         default: return VRWKV_EINVAL;
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 extern "C" int vrwkv_stream_copy(const void* src, void* dst, long bytes, void* stream) {
-    if (!src || !dst || bytes <= 0) return VRWKV_EINVAL;
+    if (any_null(src, dst) || bytes <= 0) return VRWKV_EINVAL;
     if (bytes % 16 != 0) return VRWKV_ESHAPE;
-    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) return VRWKV_EALIGN;
+    if (any_misaligned(src, dst)) return VRWKV_EALIGN;
     hipLaunchKernelGGL(stream_copy_kernel, dim3((unsigned)((bytes / 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const u32x4_t*)src, (u32x4_t*)dst, bytes / 16);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 extern "C" int vrwkv_debug_probe(int which, const float* a, const float* b, float* d, void* stream) {
-    if (!a || !d) return VRWKV_EINVAL;
+    if (any_null(a, d)) return VRWKV_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     switch (which) {
         case 0: hipLaunchKernelGGL(probe_16x16x4_f32, dim3(1), dim3(64), 0, st, a, b, d); break;
@@ -214,6 +215,5 @@ extern "C" int vrwkv_debug_probe(int which, const float* a, const float* b, floa
         case 8: hipLaunchKernelGGL(probe_dma_imm, dim3(1), dim3(64), 0, st, a, d); break;
         default: return VRWKV_EINVAL;
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }

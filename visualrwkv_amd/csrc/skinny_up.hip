@@ -38,7 +38,7 @@ void launch_r(const skup::Args& a, int NW, bool cxr, hipStream_t st) {
 extern "C" int vrwkv_skinny_up_bf16(long M, int R, int C, const void* a, const void* w, int w_is_CxR, void* out, void* stream) {
     if (M <= 0 || R <= 0 || C <= 0 || hostchk::any_null(a, w, out)) return VRWKV_EINVAL;
     if (!rank_ok(R) || C % 128 != 0) return VRWKV_ESHAPE;
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(out)) & 15u) return VRWKV_EALIGN;
+    if (hostchk::any_misaligned(a, w, out)) return VRWKV_EALIGN;
     const hipStream_t st = (hipStream_t)stream;
     const int NW = C % 256 == 0 ? 4 : 2;                  // a strip of 256 columns; 128 where C is an odd multiple of 128
     const int NS = C / (skup::WC * NW);

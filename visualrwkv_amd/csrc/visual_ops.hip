@@ -7,6 +7,9 @@
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
 #include <gfx950_prims.h>
+#include <host_checks.h>
+
+using hostchk::any_null, hostchk::finish_launch, hostchk::grid_for;
 
 namespace {
 
@@ -108,51 +111,42 @@ __global__ __launch_bounds__(256) void gelu_kernel(long nvec, const uint16_t* __
     reinterpret_cast<uint4*>(y)[i] = pack8f(o);
 }
 
-int grid_for(long nvec) {
-    long b = (nvec + 255) / 256;
-    return (int)(b < 1 ? 1 : b > 2048 ? 2048 : b);
-}
-
 }  // namespace
 
 extern "C" {
 
 int vrwkv_adaptive_pool_bf16(int B, int side_in, int side_out, int D, const void* x, void* y, void* stream) {
-    if (B <= 0 || side_in <= 0 || side_out <= 0 || !x || !y) return VRWKV_EINVAL;
+    if (B <= 0 || side_in <= 0 || side_out <= 0 || any_null(x, y)) return VRWKV_EINVAL;
     if (D <= 0 || D % 8 != 0) return VRWKV_ESHAPE;
     hipLaunchKernelGGL(adaptive_pool_kernel, dim3((unsigned)(B * side_out * side_out)), dim3(256), 0, (hipStream_t)stream,
                        side_in, side_out, D, (const uint16_t*)x, (uint16_t*)y);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 int vrwkv_gate_fwd_bf16(long n, const void* x, const void* g, void* out, void* stream) {
-    if (n <= 0 || !x || !g || !out) return VRWKV_EINVAL;
+    if (n <= 0 || any_null(x, g, out)) return VRWKV_EINVAL;
     if (n % 8 != 0) return VRWKV_ESHAPE;
     hipLaunchKernelGGL(gate_fwd_kernel, dim3(grid_for(n >> 3)), dim3(256), 0, (hipStream_t)stream, n >> 3, (const uint16_t*)x,
                        (const uint16_t*)g, (uint16_t*)out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 int vrwkv_gate_bwd_bf16(long n, const void* x, const void* g, const void* dout, void* dg, void* dx, void* stream) {
-    if (n <= 0 || !x || !g || !dout || !dg) return VRWKV_EINVAL;
+    if (n <= 0 || any_null(x, g, dout, dg)) return VRWKV_EINVAL;
     if (n % 8 != 0) return VRWKV_ESHAPE;
     hipLaunchKernelGGL(gate_bwd_kernel, dim3(grid_for(n >> 3)), dim3(256), 0, (hipStream_t)stream, n >> 3, (const uint16_t*)x,
                        (const uint16_t*)g, (const uint16_t*)dout, (uint16_t*)dg, (uint16_t*)dx);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 int vrwkv_gelu_bf16(long n, const void* x, void* y, int tanh_approx, void* stream) {
-    if (n <= 0 || !x || !y) return VRWKV_EINVAL;
+    if (n <= 0 || any_null(x, y)) return VRWKV_EINVAL;
     if (n % 8 != 0) return VRWKV_ESHAPE;
     const long nvec = n / 8, blocks = (nvec + 255) / 256;
     if (blocks > 0x7fffffffL) return VRWKV_ESHAPE;
     if (tanh_approx) hipLaunchKernelGGL(gelu_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, nvec, (const uint16_t*)x, (uint16_t*)y);
     else hipLaunchKernelGGL(gelu_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, nvec, (const uint16_t*)x, (uint16_t*)y);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? VRWKV_OK : (int)e;
+    return finish_launch();
 }
 
 }  // extern "C"

@@ -3,18 +3,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
+#include <host_checks.h>
 #include <wkv6_chunked.h>
 #include <wkv6_bwd_v2.h>
 
 namespace {
-inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+using hostchk::any_misaligned, hostchk::any_null, hostchk::finish_launch;
 inline int check6(int B, int T, int C, int H) {
     if (B <= 0 || T <= 0 || H <= 0) return VRWKV_EINVAL;
     if (C != H * 64) return VRWKV_ESHAPE;               // head size 64 (RWKV_HEAD_SIZE_A, -D_N_=64 in the reference build)
     return VRWKV_OK;
 }
 int g_bwd6_variant = -1;            // -1: default (2); 1: bwd6_kernel (wkv6_chunked.h), 2: bwd6_kernel_v2 (wkv6_bwd_v2.h)
-inline int done6() { hipError_t e = hipGetLastError(); return e == hipSuccess ? VRWKV_OK : (int)e; }
 
 // One launcher each way behind the plain and the state entries.  A state pointer that is given selects the STATE instantiation of the kernel;
 // with none given the plain instantiation runs, so the state entries with four NULLs ARE the plain entries.
@@ -22,26 +22,21 @@ int forward6(int B, int T, int C, int H, const void* r, const void* k, const voi
              const float* state0, void* y, float* state_T, float* s_ckpt, void* stream) {
     int rc = check6(B, T, C, H);
     if (rc) return rc;
-    if (!r || !k || !v || !ew || !u || !y) return VRWKV_EINVAL;
-    if (misaligned16(r) || misaligned16(k) || misaligned16(v) || misaligned16(ew) || misaligned16(u) || misaligned16(y) ||
-        (s_ckpt && misaligned16(s_ckpt)) || (state0 && misaligned16(state0)) || (state_T && misaligned16(state_T)))
-        return VRWKV_EALIGN;
+    if (any_null(r, k, v, ew, u, y)) return VRWKV_EINVAL;
+    if (any_misaligned(r, k, v, ew, u, y, s_ckpt, state0, state_T)) return VRWKV_EALIGN;      // the last three may be NULL
     wkv6c::Fwd6Args p{T, H, (const uint16_t*)r, (const uint16_t*)k, (const uint16_t*)v, ew, (const uint16_t*)u, (uint16_t*)y, s_ckpt, state0, state_T};
     const dim3 grid((unsigned)((long)B * H));
     if (state0 || state_T) hipLaunchKernelGGL(wkv6c::fwd6_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(wkv6c::fwd6_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    return done6();
+    return finish_launch();
 }
 
 int backward6(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* ew, const void* u, const void* gy,
               const float* s_ckpt, const float* d_state_T, void* gr, void* gk, void* gv, void* gw, void* gu, float* d_state0, void* stream) {
     int rc = check6(B, T, C, H);
     if (rc) return rc;
-    if (!r || !k || !v || !ew || !u || !gy || !s_ckpt || !gr || !gk || !gv || !gw || !gu) return VRWKV_EINVAL;
-    if (misaligned16(r) || misaligned16(k) || misaligned16(v) || misaligned16(ew) || misaligned16(u) || misaligned16(gy) ||
-        misaligned16(s_ckpt) || misaligned16(gr) || misaligned16(gk) || misaligned16(gv) || misaligned16(gw) || misaligned16(gu) ||
-        (d_state_T && misaligned16(d_state_T)) || (d_state0 && misaligned16(d_state0)))
-        return VRWKV_EALIGN;
+    if (any_null(r, k, v, ew, u, gy, s_ckpt, gr, gk, gv, gw, gu)) return VRWKV_EINVAL;
+    if (any_misaligned(r, k, v, ew, u, gy, s_ckpt, gr, gk, gv, gw, gu, d_state_T, d_state0)) return VRWKV_EALIGN;      // the last two may be NULL
     // wkv6_bwd_v2.h forms 32-bit byte offsets inside a tensor (the largest is the fp32 ew): a launch that reaches 4 GiB runs as batch slices of the
     // same kernel on offset pointers (every tensor is batch-major; gu and the states are per sample); one sample that large goes to the four-wave
     // kernel (64-bit)
@@ -53,11 +48,7 @@ int backward6(int B, int T, int C, int H, const void* r, const void* k, const vo
         if (bmax < 1) { v1 = true; bmax = B; }
     }
     const bool state = d_state_T || d_state0;
-    void (*kern)(wkv6c::Bwd6Args) = state ? &wkv6v2::bwd6_kernel_v2<true> : &wkv6v2::bwd6_kernel_v2<false>;      // the attribute goes on the one that is launched
-    if (!v1) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(wkv6v2::Lds6V2));
-        if (e != hipSuccess) return (int)e;
-    }
+    void (*kern)(wkv6c::Bwd6Args) = state ? &wkv6v2::bwd6_kernel_v2<true> : &wkv6v2::bwd6_kernel_v2<false>;
     const size_t act = (size_t)T * C, ck = (size_t)H * ((T + 15) / 16) * 64 * 64, st = (size_t)H * 64 * 64;
     for (int b0 = 0; b0 < B; b0 += bmax) {
         const int nb = B - b0 < bmax ? B - b0 : bmax;
@@ -66,10 +57,9 @@ int backward6(int B, int T, int C, int H, const void* r, const void* k, const vo
                           (const uint16_t*)gy + o, s_ckpt + (size_t)b0 * ck, (uint16_t*)gr + o, (uint16_t*)gk + o, (uint16_t*)gv + o, (uint16_t*)gw + o,
                           (uint16_t*)gu + (size_t)b0 * C, d_state_T ? d_state_T + (size_t)b0 * st : nullptr, d_state0 ? d_state0 + (size_t)b0 * st : nullptr};
         const dim3 grid((unsigned)((long)nb * H));
-        if (!v1) hipLaunchKernelGGL(kern, grid, dim3(768), sizeof(wkv6v2::Lds6V2), (hipStream_t)stream, p);
-        else if (state) hipLaunchKernelGGL(wkv6c::bwd6_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(wkv6c::bwd6_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
-        const int rc2 = done6();
+        if (state && v1) hipLaunchKernelGGL(wkv6c::bwd6_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        else if (v1) hipLaunchKernelGGL(wkv6c::bwd6_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        const int rc2 = v1 ? finish_launch() : hostchk::launch_lds(kern, grid, dim3(768), sizeof(wkv6v2::Lds6V2), (hipStream_t)stream, p);
         if (rc2) return rc2;
     }
     return VRWKV_OK;

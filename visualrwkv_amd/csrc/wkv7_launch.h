@@ -20,19 +20,12 @@ constexpr int BWD_V5_MODE = 2 + 4 + 128;
 using hostchk::any_misaligned;
 using hostchk::any_null;
 using hostchk::finish_launch;
+using hostchk::launch_lds;
 using hostchk::misaligned;
 inline int check_common(int B, int T, int H) {
     if (B <= 0 || T <= 0 || H <= 0) return VRWKV_EINVAL;
     if (T % VRWKV_CHUNK_LEN != 0) return VRWKV_ESHAPE;   // cuda_backward asserts this, wkv7_cuda.cu:136
     return VRWKV_OK;
-}
-// dynamic-LDS launch of a kernel taking one argument block
-template <class Args>
-inline int launch_lds(void (*kern)(Args), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Args& p) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, p);
-    return finish_launch();
 }
 
 // The argument block of a forward launch from the tensors every forward entry takes; s0, s_final, chunk_reset and dbg are set by the entry that has them.
