@@ -311,6 +311,20 @@ int vrwkv_decode_tmix_head_bf16(int B, int H, const void* r, const void* k, cons
                                 const void* w0, const void* a0, const void* v0, const void* k_k, const void* k_a,
                                 const void* r_k, const void* ln_w, const void* ln_b, float eps,
                                 float* state, void* out, const void* carry_src, void* carry_dst, void* stream);
+/* Sampling head of the decode step: what the reference's applications do with the logits of VisualRWKV.generate's model pass
+ * (src/model.py:496-530, whose own do_sample branch raises) -- PIPELINE.sample_logits of the `rwkv` package -- as one kernel, one
+ * workgroup per row, made deterministic.  For row b of logits (B,V) bf16, params = {temperature > 0, top_p >= 0} and u[b] in [0, 1), all
+ * three read from DEVICE memory (one captured graph serves every setting):
+ *   p = softmax(l);  K = { i : p_i >= c }, c the first value in descending order whose running sum reaches top_p (ties with c kept;
+ *   top_p = 0: the maximum and its ties; top_p >= 1: every token);  q_i = exp((l_i - max l) / temperature) on K;
+ *   token[b] = the first i in K, in index order, with sum_{j <= i, j in K} q_j > u[b] sum_K q (no such prefix: the last member of K
+ *   of weight > 0);  logit_prob[b] = { l_token (exact), exp(l_token - max l) / sum exp(l - max l) } in fp32.
+ * Entries equal to -inf have weight 0; rows holding NaN or +inf are undefined (no access out of bounds).  With emb (V,C) bf16 and x_out
+ * (B,C) bf16 (both or neither NULL) the row emb[token[b]] is copied to x_out[b]: the next step's input.  Every sum has a fixed order:
+ * a second call on the same inputs is bit-identical.  V % 8 == 0, V <= 65536 (the row stays on chip: VRWKV_ESHAPE above), C % 8 == 0 (C is
+ * checked with or without emb); logits, emb, x_out 16-byte aligned, params, u, token, logit_prob 4-byte aligned. */
+int vrwkv_sample_pick_bf16(int B, int V, int C, const void* logits, const float* params, const float* u, const void* emb,
+                           void* x_out, int* token, float* logit_prob, void* stream);
 
 /* WKV7 single-token step with carried state (stateful generation; the reference re-runs the whole forward per new
  * token, VisualRWKV-v7/v7.00/src/model.py:513-529).  w..a, y: (B,H,64) bf16; state: (B,H,64,64) f32, S[i][j] with

@@ -21,7 +21,7 @@ HOST_LIB_PATH = os.path.join(PKG_DIR, "libvisualrwkv_host.so")    # the op's CPU
 HASH_PATH = LIB_PATH + ".hash"      # content hash of the sources the library was built from; travels with it
 ARCH = "gfx950"
 
-SOURCES = ["wkv7_capi.hip", "wkv7_profile.hip", "wkv7_host.hip", "probe.hip", "fused_ops.hip", "tmix_fused.hip", "attention.hip", "wkv7_step.hip", "ln_fused.hip", "wkv6_capi.hip", "loss_fused.hip", "gemv_decode.hip", "decode_fused.hip", "wkv6_step.hip", "decode6_fused.hip", "lora_wgrad.hip", "skinny_up.hip", "visual_ops.hip", "patch_embed.hip", "image_ops.hip"]
+SOURCES = ["wkv7_capi.hip", "wkv7_profile.hip", "wkv7_host.hip", "probe.hip", "fused_ops.hip", "tmix_fused.hip", "attention.hip", "wkv7_step.hip", "ln_fused.hip", "wkv6_capi.hip", "loss_fused.hip", "gemv_decode.hip", "decode_fused.hip", "wkv6_step.hip", "decode6_fused.hip", "lora_wgrad.hip", "skinny_up.hip", "visual_ops.hip", "patch_embed.hip", "image_ops.hip", "sample_head.hip"]
 
 
 def hipcc() -> str:

@@ -686,40 +686,58 @@ class RWKV(nn.Module):
         advanced in place by every call, exactly as `forward_stateful(x_emb, state, last_only=True)` would."""
         return GraphDecoder(self, state)
 
-    def decoder_for(self, state):
+    def decoder_for(self, state, sampled=False):
         """`make_decoder` with the captured graph re-used across prompts: one capture per (batch size, device, parameter
-        versions); later calls copy `state` into the graph's own state tensors.  The returned decoder advances ITS
-        state (`decoder.state`), not the argument."""
+        versions, sampled); later calls copy `state` into the graph's own state tensors.  The returned decoder advances ITS
+        state (`decoder.state`), not the argument.  sampled: the step ends in the pick kernel (GraphDecoder.sample)."""
         S0 = state.S[0]
         from . import param_state
-        key = (S0.shape[0], S0.device, sum(p._version for p in self.parameters()), param_state.generation())
+        key = (S0.shape[0], S0.device, sum(p._version for p in self.parameters()), param_state.generation(), bool(sampled))
         cache = self.__dict__.setdefault("_decoders", {})
         dec = cache.get(key)
         if dec is None:
-            cache.clear()                                 # parameters changed (or first use): stale graphs go
-            dec = cache[key] = GraphDecoder(self, state)
+            for k in [k for k in cache if k[:4] != key[:4]]:      # parameters changed (or first use): stale graphs go
+                del cache[k]
+            dec = cache[key] = GraphDecoder(self, state, sampled=sampled)
         elif dec.state is not state:
             dec.load_state(state)
         return dec
 
 
 class GraphDecoder:
-    def __init__(self, rwkv: "RWKV", state: RWKV7State):
-        self.rwkv, self.state = rwkv, state
+    """sampled=False: `__call__(x_emb) -> logits`.  sampled=True: the captured chain ends in the pick kernel (sampling.py), which turns the
+    logits into the token, its logit and probability (self.pick) and writes the token's embedding row into x_in -- the next replay's input,
+    in stream order; a generated token is `sample(u)`: one small device-to-device copy, one replay, one read-back."""
+    def __init__(self, rwkv: "RWKV", state: RWKV7State, sampled=False):
+        self.rwkv, self.state, self.sampled = rwkv, state, sampled
         p = next(rwkv.parameters())
         B = state.S[0].shape[0]
         self.x_in = torch.zeros(B, 1, rwkv.args.n_embd, device=p.device, dtype=p.dtype)
+        if sampled:
+            from . import sampling
+            self.pick = sampling.PickBuffers(B, p.device)      # params, u, token, logit_prob at fixed addresses
+
+            def step():
+                logits, _ = rwkv.forward_stateful(self.x_in, state, last_only=True)
+                if not sampling.kernel_supported(logits, rwkv.emb.weight, self.x_in):
+                    raise RuntimeError("GraphDecoder(sampled=True): the pick kernel takes bf16 logits of a vocabulary that is a multiple of 8 "
+                                       f"and at most {sampling.MAX_V}, and a bf16 embedding (got {tuple(logits.shape)} {logits.dtype})")
+                sampling.launch_pick(logits, self.pick, rwkv.emb.weight, self.x_in)
+                return logits
+        else:
+            def step():
+                return rwkv.forward_stateful(self.x_in, state, last_only=True)[0]
         keep = [t.clone() for t in state.att_x + state.ffn_x + state.S]       # warm-up and capture run the step for real
         fresh, n_tok = list(state.fresh), state.n_tokens
         side = torch.cuda.Stream(device=p.device)
         side.wait_stream(torch.cuda.current_stream(p.device))
         with torch.cuda.stream(side), torch.no_grad():
             for _ in range(2):
-                rwkv.forward_stateful(self.x_in, state, last_only=True)
+                step()
         torch.cuda.current_stream(p.device).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.logits, _ = rwkv.forward_stateful(self.x_in, state, last_only=True)
+            self.logits = step()
         for dst, src in zip(state.att_x + state.ffn_x + state.S, keep):
             dst.copy_(src)
         state.fresh, state.n_tokens = fresh, n_tok
@@ -739,3 +757,14 @@ class GraphDecoder:
         self.state.n_tokens += 1
         self.state.fresh = [False] * len(self.state.fresh)
         return self.logits
+
+    @torch.no_grad()
+    def sample(self, u):
+        """One generated token of the sampled decoder: u (B,) on the device -> (token int32 (B,), logit (B,), prob (B,)) on the host.  The input
+        is what the previous pick (a replay's, or the caller's eager first one with x_out = x_in) left in x_in; temperature and top_p are
+        what `self.pick.set` last wrote."""
+        self.pick.u.copy_(u)
+        self.graph.replay()
+        self.state.n_tokens += 1
+        self.state.fresh = [False] * len(self.state.fresh)
+        return self.pick.read()

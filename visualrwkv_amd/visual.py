@@ -548,13 +548,47 @@ class VisualRWKV(nn.Module):
                 x.backward(gx)
         return total
 
+    @staticmethod
+    def _sample_uniforms(max_new_tokens, B, generator, device):
+        """Every u of a sampled call, drawn up front: (max_new_tokens, B) fp32 on `device`."""
+        u = torch.rand(max_new_tokens, B, generator=generator, device=generator.device if generator is not None else "cpu")
+        return u.to(device=device, dtype=torch.float32)
+
+    @staticmethod
+    def _sampled_append(out, triple, done, stop_token_idx):
+        """One step's (token, logit, prob) rows into the result lists -- scalars for one row, lists of B values otherwise -- and whether
+        the call is over: every row has produced the stop token."""
+        tok, lg, pr = (t.tolist() for t in triple)
+        for lst, v in zip(out, (tok, lg, pr)):
+            lst.append(v[0] if len(v) == 1 else v)
+        for b, t in enumerate(tok):
+            done[b] = done[b] or t == stop_token_idx
+        return all(done)
+
     @torch.no_grad()
-    def generate(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx):
-        """Greedy decoding with the reference's semantics (src/model.py:496-530): the full sequence is
-        re-run for every new token (stateful decoding is SURVEY.md 8f rank 1)."""
-        if do_sample:
-            raise NotImplementedError
+    def generate(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx, generator=None):
+        """Decoding with the reference's semantics (src/model.py:496-530): the full sequence is re-run for every new token (stateful
+        decoding is SURVEY.md 8f rank 1).  Greedy, or with do_sample the top-p / temperature pick of sampling.py on each step's last row
+        (the reference raises there; its applications sample); generator: the torch.Generator of the call's uniform numbers."""
         samples = {"input_ids": input_ids, "images": images, "labels": torch.full_like(input_ids, IGNORE_INDEX)}
+        if do_sample:
+            from . import sampling
+            sampling.check_args(temperature, top_p)
+            x, _, mk, _ = _embed(self, samples)
+            mk.pop("n_image", None)
+            B = x.size(0)
+            u_all = self._sample_uniforms(max_new_tokens, B, generator, x.device)
+            out, done = ([], [], []), [False] * B
+            for i in range(max_new_tokens):
+                logits = self.rwkv(x, **mk)[:, -1, :].contiguous()
+                nxt = torch.empty(B, 1, x.size(-1), device=x.device, dtype=x.dtype)
+                triple = sampling.pick(logits, temperature, top_p, u_all[i], self.rwkv.emb.weight.to(x.dtype), nxt)
+                if self._sampled_append(out, triple, done, stop_token_idx):
+                    break
+                x = torch.cat((x, nxt), dim=-2)[:, -self.args.ctx_len:, :]
+                if "mask" in mk:
+                    mk["mask"] = torch.cat((mk["mask"], torch.zeros_like(mk["mask"][:, -1:])), dim=1)[:, -self.args.ctx_len:, :]
+            return out
         x, _, mk, _ = _embed(self, samples)
         mk.pop("n_image", None)
         toks, lgs, prs = [], [], []
@@ -573,14 +607,16 @@ class VisualRWKV(nn.Module):
 
     @torch.no_grad()
     def generate_stateful(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx,
-                          use_graph=None):
+                          use_graph=None, generator=None):
         """`generate` with the recurrent state carried between tokens: one prefill over the prompt, then one
         single-token step per new token (O(1) per token instead of re-running the whole sequence).
         The prompt is left-padded once, like `RWKV.forward` pads it (src/model.py:301-307), so the first token
         is the one `generate` returns; later tokens are conditioned on that same fixed prefix, whereas the
-        reference's per-step re-padding changes the number of pad tokens as the sequence grows."""
-        if do_sample:
-            raise NotImplementedError
+        reference's per-step re-padding changes the number of pad tokens as the sequence grows.
+        do_sample: the pick of sampling.py instead of the argmax, with the call's uniform numbers drawn up front from `generator`.  Through
+        the captured graph (bf16, fused, B <= 4) the pick is the step's last kernel and writes the next input itself: a token is one
+        replay and one read-back; otherwise sampling.pick per token.  Several rows: every list entry holds B values, and the call ends
+        when every row has produced the stop token."""
         if getattr(self, "vrwkv", None) is not None:
             raise NotImplementedError("generate_stateful with args.n_vrwkv_layer: only the embedding differs, but the stateful path has not been "
                                       "shown equal to generate() with the vision encoder in front of it; use generate()")
@@ -598,6 +634,8 @@ class VisualRWKV(nn.Module):
         if use_graph is None:                            # captured step where the batched-GEMV decode path applies
             use_graph = (x.is_cuda and bool(getattr(self.args, "fused", False)) and x.dtype == torch.bfloat16 and x.size(0) <= 4
                          and max_new_tokens >= 8)
+        if do_sample:
+            return self._generate_stateful_sampled(logits, state, temperature, top_p, max_new_tokens, stop_token_idx, use_graph, generator)
         decoder = self.rwkv.decoder_for(state) if use_graph and x.is_cuda else None     # one capture per batch size, re-used
         toks, lgs, prs = [], [], []
         for _ in range(max_new_tokens):
@@ -612,3 +650,31 @@ class VisualRWKV(nn.Module):
             else:
                 logits, state = self.rwkv.forward_stateful(self.rwkv.emb(nxt), state, last_only=True)
         return toks, lgs, prs
+
+    def _generate_stateful_sampled(self, logits, state, temperature, top_p, max_new_tokens, stop_token_idx, use_graph, generator):
+        from . import sampling
+        sampling.check_args(temperature, top_p)
+        B = logits.size(0)
+        emb = self.rwkv.emb.weight
+        u_all = self._sample_uniforms(max_new_tokens, B, generator, logits.device)
+        logits = logits.contiguous()
+        use_graph = bool(use_graph) and logits.is_cuda and sampling.kernel_supported(logits, emb)
+        out, done = ([], [], []), [False] * B
+        if use_graph:
+            decoder = self.rwkv.decoder_for(state, sampled=True)
+            decoder.pick.set(temperature, top_p)
+            # the first token eagerly, from the prefill's logits, into the graph's input
+            triple = sampling.pick(logits, temperature, top_p, u_all[0], emb, decoder.x_in)
+            for i in range(1, max_new_tokens + 1):
+                if self._sampled_append(out, triple, done, stop_token_idx) or i == max_new_tokens:
+                    break
+                triple = decoder.sample(u_all[i])
+            return out
+        nxt = torch.empty(B, 1, emb.size(1), device=logits.device, dtype=logits.dtype)
+        for i in range(max_new_tokens):
+            triple = sampling.pick(logits, temperature, top_p, u_all[i], emb.to(logits.dtype), nxt)
+            if self._sampled_append(out, triple, done, stop_token_idx) or i == max_new_tokens - 1:
+                break
+            logits, state = self.rwkv.forward_stateful(nxt, state, last_only=True)
+            logits = logits.contiguous()
+        return out
