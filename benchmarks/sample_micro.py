@@ -5,6 +5,10 @@
 (b) ms per generated token of the 1.5B stack: the sampled captured step (GraphDecoder.sample: copy of u, replay, one read-back) against the
     greedy loop of VisualRWKV.generate_stateful (argmax / gather / softmax with three `.item()`, emb, copy, replay), legs alternating in one
     process.  The greedy leg is the loop as it stands in visual.py, which sampling left untouched.
+(c) presence / count penalties (vrwkv_sample_pick_pen_bf16): the plain and the penalised kernel alternated at B = 1 and 4 (occ with 256
+    counted tokens per row), and per generated token, alternated with (b)'s legs: the penalised captured step
+    (GraphDecoder(penalised=True)) and what the penalties cost without it -- the unsampled captured step, the penalties in torch on its
+    logits, sampling.pick with the embedding row as x_out, the counts updated in torch, the embedding fed back (`penalised_by_hand`).
 python benchmarks/sample_micro.py [n_tokens] [rounds]      one JSON line."""
 import json
 import os
@@ -66,6 +70,14 @@ def kernel_leg(res):
             bufs.set(tau, top_p)
             bufs.u.copy_(u)
             res[f"pick_kernel_us_B{B}_{name}"] = events_us(lambda: sampling.launch_pick(logits, bufs, emb, x_out))
+        occ = torch.zeros(B, V, device="cuda")
+        occ[:, torch.randperm(V, generator=g)[:256].cuda()] = 1.5
+        bufs.set(1.0, 0.9, 0.4, 0.4, 0.996)
+        pair = {"plain": [], "pen": []}
+        for _ in range(5):                                   # alternated: the same clocks and neighbours for both
+            pair["plain"].append(events_us(lambda: sampling.launch_pick(logits, bufs, emb, x_out), reps=3)["median"])
+            pair["pen"].append(events_us(lambda: sampling.launch_pick(logits, bufs, emb, x_out, occ), reps=3)["median"])
+        res[f"pick_kernel_alternated_us_B{B}"] = {k: spread(v) for k, v in pair.items()}
         res[f"pick_torch_us_B{B}"] = events_us(lambda: sampling.pick_torch(logits, 1.0, 0.9, u, emb, x_out), calls=10)
 
         def greedy_device():
@@ -112,7 +124,30 @@ def token_leg(res, n, rounds):
             for i in range(k):
                 sampled_dec.sample(u_all[i])
 
-        legs = {"greedy": greedy, "sampled": sampled}
+        _, st3 = m.forward_stateful(prompt, None, last_only=True)
+        pen_dec = m.decoder_for(st3, sampled=True, penalised=True)
+        pen_dec.pick.set(1.0, 0.9, 0.4, 0.4, 0.996)
+        occ_hand = torch.zeros(1, V, device="cuda")
+        nxt = torch.empty(1, 1, C, device="cuda", dtype=torch.bfloat16)
+
+        def penalised(k):
+            pen_dec.pick.reset()
+            sampling.pick(logits0.contiguous(), 1.0, 0.9, u_all[0], m.emb.weight, pen_dec.x_in, pen_dec.pick.occ, 0.4, 0.4, 0.996)
+            for i in range(k):
+                pen_dec.sample(u_all[i])
+
+        def penalised_by_hand(k):
+            occ_hand.zero_()
+            logits = logits0
+            for i in range(k):
+                l = torch.where(occ_hand > 0, (logits.float() - (0.4 + occ_hand * 0.4)).bfloat16(), logits)
+                triple = sampling.pick(l, 1.0, 0.9, u_all[i], m.emb.weight, nxt)
+                occ_hand.mul_(0.996)
+                occ_hand[0, triple[0].long()] += 1.0
+                [t.tolist() for t in triple]                 # the step's read-back, as generate_stateful's eager loop does it
+                logits = greedy_dec(nxt)
+
+        legs = {"greedy": greedy, "sampled": sampled, "penalised": penalised, "penalised_by_hand": penalised_by_hand}
         for fn in legs.values():
             fn(8)
         times = {k: [] for k in legs}
@@ -124,6 +159,7 @@ def token_leg(res, n, rounds):
                 times[name].append((time.perf_counter() - t0) * 1e3 / n)
         for name in legs:
             res[f"{name}_ms_per_token"] = spread(times[name])
+        res["penalised_minus_sampled_ms_per_token"] = spread([b - a for a, b in zip(times["sampled"], times["penalised"])])
 
 
 def main():

@@ -325,6 +325,22 @@ int vrwkv_decode_tmix_head_bf16(int B, int H, const void* r, const void* k, cons
  * checked with or without emb); logits, emb, x_out 16-byte aligned, params, u, token, logit_prob 4-byte aligned. */
 int vrwkv_sample_pick_bf16(int B, int V, int C, const void* logits, const float* params, const float* u, const void* emb,
                            void* x_out, int* token, float* logit_prob, void* stream);
+/* The same pick under the presence / count penalties and the token ban that the reference's applications put around sample_logits
+ * (VisualRWKV-v7/v7.10/app/app_gpu.py:56-86: `for n in occurrence: out[n] -= alpha_presence + occurrence[n] * alpha_frequency`, the pick,
+ * `occurrence[n] *= 0.996`, `occurrence[token] += 1`; token_ban), with the occurrence counts as a dense occ (B,V) fp32 in device memory,
+ * updated in place.  params = {temperature, top_p, alpha_presence, alpha_count, decay}, five fp32 in device memory.  For row b and element i,
+ * with c = occ[b,i] as read:
+ *   c < 0 (banned):  l'_i = -inf; occ[b,i] keeps its bits (no decay).
+ *   c == 0:          l'_i = l_i; occ[b,i] unchanged.
+ *   c > 0:           l'_i = bf16_rne(fp32(l_i) - (alpha_presence + c * alpha_count)), product, sum and difference each rounded to fp32 (what
+ *                    `out[n] -= ...` does on a bf16 tensor; the row stays bf16);  occ[b,i] <- fl32(c * decay).
+ * The pick of vrwkv_sample_pick_bf16 then runs on l', bit for bit what that entry returns for the row l'; logit_prob[b] holds l'_token and
+ * its probability under softmax(l').  Then occ[b,token] <- (its value after the step above) + 1 in fp32: a first occurrence gives exactly 1.
+ * A row with no weight anywhere (every entry banned or -inf: undefined, as in the plain entry) gets no + 1.  Row b of occ is read and
+ * written by row b's workgroup only.  Checks as in vrwkv_sample_pick_bf16 and in its order, with occ among the pointers that must not be
+ * NULL (VRWKV_EINVAL) and among the 16-byte aligned ones (VRWKV_EALIGN). */
+int vrwkv_sample_pick_pen_bf16(int B, int V, int C, const void* logits, const float* params, const float* u, float* occ, const void* emb,
+                               void* x_out, int* token, float* logit_prob, void* stream);
 
 /* WKV7 single-token step with carried state (stateful generation; the reference re-runs the whole forward per new
  * token, VisualRWKV-v7/v7.00/src/model.py:513-529).  w..a, y: (B,H,64) bf16; state: (B,H,64,64) f32, S[i][j] with

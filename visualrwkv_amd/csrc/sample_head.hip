@@ -11,6 +11,10 @@
 // 16 rounds of "mass of the keys >= t" over exp values kept in registers.  Every sum has a fixed order (per thread in index order, the
 // wave's butterfly, the 16 wave partials in sequence; the scan: lanes in sequence, then waves in sequence): no atomics, a second launch
 // on the same inputs is bit-identical.  temperature, top_p and u come from device memory: a captured graph serves every setting.
+// sample_pick_kernel<true> (vrwkv_sample_pick_pen_bf16) is the same body on the row l' that the applications' occurrence counts make of l
+// (VisualRWKV-v7/v7.10/app/app_gpu.py:56-86): the owner of a chunk reads its 2 x 16 bytes of occ while it turns the chunk into keys -- banned
+// (c < 0): -inf; counted (c > 0): bf16(l - (alpha_presence + c alpha_count)), and c decay goes back -- and the winning thread, which owns the
+// token's chunk, adds 1 to the token's count after its own decayed store.  Row b of occ is touched by workgroup b alone; no barrier is added.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/visualrwkv_hip.h"
@@ -36,6 +40,7 @@ struct PickArgs {
     uint16_t* x_out;
     int* token;
     float* logit_prob;
+    float* occ;                                              // the penalised entry's counts; NULL in the plain one
 };
 
 enum { OP_SUM, OP_MAX, OP_MIN };
@@ -73,7 +78,29 @@ DEVFN uint32_t key_at(const vrwkv_u4& k, int j) {
     return (j & 1) ? w >> 16 : w & 0xffffu;
 }
 
-__global__ __launch_bounds__(SP_THREADS) void sample_pick_kernel(PickArgs a) {
+// One logit (bf16 bits) under the count c of its token: banned -> -inf; counted -> l - (alpha_presence + c alpha_count) rounded to bf16 as
+// `out[n] -= ...` rounds on a bf16 tensor.  Product, sum and difference are each rounded on their own, as in torch.
+DEVFN uint32_t penalised(uint32_t h, float c, float a_presence, float a_count) {
+#pragma clang fp contract(off)
+    if (c < 0.f) return 0xff80u;
+    if (c > 0.f) {
+        const float pen = a_presence + c * a_count;
+        h = f32_to_bf16_bits(bf16_to_f32((uint16_t)h) - pen);
+    }
+    return h;
+}
+DEVFN uint32_t penalised2(uint32_t w, float c_lo, float c_hi, float a_presence, float a_count) {
+    return penalised(w & 0xffffu, c_lo, a_presence, a_count) | (penalised(w >> 16, c_hi, a_presence, a_count) << 16);
+}
+DEVFN float decayed(float c, float decay) { return c > 0.f ? c * decay : c; }
+// four counts after a pick; whether one of them changed (their 16 bytes go back only then)
+DEVFN bool decay4(f32x4& o, float decay) {
+    const bool any = o.x > 0.f || o.y > 0.f || o.z > 0.f || o.w > 0.f;
+    o = f32x4{decayed(o.x, decay), decayed(o.y, decay), decayed(o.z, decay), decayed(o.w, decay)};
+    return any;
+}
+
+template <bool PEN> __global__ __launch_bounds__(SP_THREADS) void sample_pick_kernel(PickArgs a) {
     __shared__ float red[SP_WAVES];
     __shared__ float wtot[SP_WAVES];
     __shared__ float tot[SP_THREADS];
@@ -94,6 +121,17 @@ __global__ __launch_bounds__(SP_THREADS) void sample_pick_kernel(PickArgs a) {
 #pragma unroll
     for (int i = 0; i < SP_MAXCH; ++i) {
         if (i < cpt) {
+            if constexpr (PEN) {
+                if (c0 + i < nvec) {                         // the chunk's counts, consumed here: a second copy of the row in registers spills
+                    f32x4* const oc = reinterpret_cast<f32x4*>(a.occ + (size_t)b * a.V + (size_t)(c0 + i) * 8);
+                    f32x4 o0 = oc[0], o1 = oc[1];
+                    const float ap = a.params[2], ac = a.params[3], decay = a.params[4];
+                    raw[i] = vrwkv_u4{penalised2(raw[i].x, o0.x, o0.y, ap, ac), penalised2(raw[i].y, o0.z, o0.w, ap, ac),
+                                      penalised2(raw[i].z, o1.x, o1.y, ap, ac), penalised2(raw[i].w, o1.z, o1.w, ap, ac)};
+                    if (decay4(o0, decay)) oc[0] = o0;
+                    if (decay4(o1, decay)) oc[1] = o1;
+                }
+            }
             const vrwkv_u4 k = vrwkv_u4{keys_of(raw[i].x), keys_of(raw[i].y), keys_of(raw[i].z), keys_of(raw[i].w)};
             kl[i * SP_THREADS] = k;
 #pragma unroll
@@ -197,6 +235,14 @@ __global__ __launch_bounds__(SP_THREADS) void sample_pick_kernel(PickArgs a) {
         a.token[b] = token;
         a.logit_prob[2 * b] = l;
         a.logit_prob[2 * b + 1] = exp2_scaled(l - m, SP_LOG2E, SP_LOG2E_LO) / Z;
+        if constexpr (PEN) {
+            if (win < 2 * SP_MAXV) {                         // this thread owns the token's chunk: the read follows its own decayed store
+                f32x4* const oc = reinterpret_cast<f32x4*>(a.occ + (size_t)b * a.V + (size_t)(token & ~3));
+                f32x4 o = *oc;
+                o[token & 3] += 1.f;
+                *oc = o;
+            }
+        }
     }
     if (a.emb) {
         const uint16_t* src = a.emb + (size_t)token * a.C;
@@ -207,18 +253,31 @@ __global__ __launch_bounds__(SP_THREADS) void sample_pick_kernel(PickArgs a) {
 
 inline bool off4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
 
+// both entries: the checks in the order count, shape, NULL, alignment, then the launch
+int pick_entry(bool pen, int B, int V, int C, const void* logits, const float* params, const float* u, float* occ, const void* emb, void* x_out,
+               int* token, float* logit_prob, void* stream) {
+    if (B <= 0) return VRWKV_EINVAL;
+    if (V <= 0 || V % 8 != 0 || V > SP_MAXV || C <= 0 || C % 8 != 0) return VRWKV_ESHAPE;
+    if (hostchk::any_null(logits, params, u, token, logit_prob) || (pen && occ == nullptr) || (emb == nullptr) != (x_out == nullptr))
+        return VRWKV_EINVAL;
+    // the row, its counts, the embedding and x_out move in 16-byte pieces; the scalars by element
+    if (hostchk::any_misaligned(logits, occ, emb, x_out) || off4(params) || off4(u) || off4(token) || off4(logit_prob)) return VRWKV_EALIGN;
+    PickArgs a{};
+    a.V = V; a.C = C; a.logits = (const uint16_t*)logits; a.params = params; a.u = u;
+    a.emb = (const uint16_t*)emb; a.x_out = (uint16_t*)x_out; a.token = token; a.logit_prob = logit_prob; a.occ = occ;
+    const size_t lds = (size_t)((V / 8 + SP_THREADS - 1) / SP_THREADS) * SP_THREADS * 16;      // the row's keys: up to 128 KB
+    return hostchk::launch_lds(pen ? sample_pick_kernel<true> : sample_pick_kernel<false>, dim3((unsigned)B), dim3(SP_THREADS), lds,
+                               (hipStream_t)stream, a);
+}
+
 }  // namespace
 
 extern "C" int vrwkv_sample_pick_bf16(int B, int V, int C, const void* logits, const float* params, const float* u, const void* emb,
                                       void* x_out, int* token, float* logit_prob, void* stream) {
-    if (B <= 0) return VRWKV_EINVAL;
-    if (V <= 0 || V % 8 != 0 || V > SP_MAXV || C <= 0 || C % 8 != 0) return VRWKV_ESHAPE;
-    if (hostchk::any_null(logits, params, u, token, logit_prob) || (emb == nullptr) != (x_out == nullptr)) return VRWKV_EINVAL;
-    // the row, the embedding and x_out move in 16-byte pieces; the scalars by element
-    if (hostchk::any_misaligned(logits, emb, x_out) || off4(params) || off4(u) || off4(token) || off4(logit_prob)) return VRWKV_EALIGN;
-    PickArgs a{};
-    a.V = V; a.C = C; a.logits = (const uint16_t*)logits; a.params = params; a.u = u;
-    a.emb = (const uint16_t*)emb; a.x_out = (uint16_t*)x_out; a.token = token; a.logit_prob = logit_prob;
-    const size_t lds = (size_t)((V / 8 + SP_THREADS - 1) / SP_THREADS) * SP_THREADS * 16;      // the row's keys: up to 128 KB
-    return hostchk::launch_lds(sample_pick_kernel, dim3((unsigned)B), dim3(SP_THREADS), lds, (hipStream_t)stream, a);
+    return pick_entry(false, B, V, C, logits, params, u, nullptr, emb, x_out, token, logit_prob, stream);
+}
+
+extern "C" int vrwkv_sample_pick_pen_bf16(int B, int V, int C, const void* logits, const float* params, const float* u, float* occ,
+                                          const void* emb, void* x_out, int* token, float* logit_prob, void* stream) {
+    return pick_entry(true, B, V, C, logits, params, u, occ, emb, x_out, token, logit_prob, stream);
 }

@@ -60,6 +60,7 @@ PROTOTYPES = {
     "vrwkv_gemv_multi_copy_bf16": (_c_int, [_c_int, _c_int] + [_c_void_p] * 9 + [_c_long] + [_c_void_p]),
     "vrwkv_gemv_gated_copy_bf16": (_c_int, [_c_int, _c_int] + [_c_void_p] * 10 + [_c_long] + [_c_void_p]),
     "vrwkv_sample_pick_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 8),
+    "vrwkv_sample_pick_pen_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 9),
     "vrwkv_wkv6_step_bf16": (_c_int, [_c_int] * 2 + [_c_void_p] * 8),
     "vrwkv_decode6_ddlerp_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 7),
     "vrwkv_decode6_tmix_head_bf16": (_c_int, [_c_int] * 3 + [_c_void_p] * 10 + [_c_float] + [_c_void_p] * 3),

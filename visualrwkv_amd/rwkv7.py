@@ -686,19 +686,20 @@ class RWKV(nn.Module):
         advanced in place by every call, exactly as `forward_stateful(x_emb, state, last_only=True)` would."""
         return GraphDecoder(self, state)
 
-    def decoder_for(self, state, sampled=False):
+    def decoder_for(self, state, sampled=False, penalised=False):
         """`make_decoder` with the captured graph re-used across prompts: one capture per (batch size, device, parameter
-        versions, sampled); later calls copy `state` into the graph's own state tensors.  The returned decoder advances ITS
-        state (`decoder.state`), not the argument.  sampled: the step ends in the pick kernel (GraphDecoder.sample)."""
+        versions, sampled, penalised); later calls copy `state` into the graph's own state tensors.  The returned decoder advances ITS
+        state (`decoder.state`), not the argument.  sampled: the step ends in the pick kernel (GraphDecoder.sample); penalised: in the
+        pick under presence / count penalties and a token ban, on the decoder's own occurrence counts (decoder.pick.occ)."""
         S0 = state.S[0]
         from . import param_state
-        key = (S0.shape[0], S0.device, sum(p._version for p in self.parameters()), param_state.generation(), bool(sampled))
+        key = (S0.shape[0], S0.device, sum(p._version for p in self.parameters()), param_state.generation(), bool(sampled), bool(penalised))
         cache = self.__dict__.setdefault("_decoders", {})
         dec = cache.get(key)
         if dec is None:
             for k in [k for k in cache if k[:4] != key[:4]]:      # parameters changed (or first use): stale graphs go
                 del cache[k]
-            dec = cache[key] = GraphDecoder(self, state, sampled=sampled)
+            dec = cache[key] = GraphDecoder(self, state, sampled=sampled, penalised=penalised)
         elif dec.state is not state:
             dec.load_state(state)
         return dec
@@ -707,22 +708,27 @@ class RWKV(nn.Module):
 class GraphDecoder:
     """sampled=False: `__call__(x_emb) -> logits`.  sampled=True: the captured chain ends in the pick kernel (sampling.py), which turns the
     logits into the token, its logit and probability (self.pick) and writes the token's embedding row into x_in -- the next replay's input,
-    in stream order; a generated token is `sample(u)`: one small device-to-device copy, one replay, one read-back."""
-    def __init__(self, rwkv: "RWKV", state: RWKV7State, sampled=False):
-        self.rwkv, self.state, self.sampled = rwkv, state, sampled
+    in stream order; a generated token is `sample(u)`: one small device-to-device copy, one replay, one read-back.  penalised=True (with
+    sampled): that last kernel is the penalised pick on self.pick.occ (B, V), the run's occurrence counts, which it updates itself;
+    `self.pick.reset(token_ban)` starts a run."""
+    def __init__(self, rwkv: "RWKV", state: RWKV7State, sampled=False, penalised=False):
+        if penalised and not sampled:
+            raise ValueError("GraphDecoder(penalised=True) goes with sampled=True: the penalties are part of the pick")
+        self.rwkv, self.state, self.sampled, self.penalised = rwkv, state, sampled, penalised
         p = next(rwkv.parameters())
         B = state.S[0].shape[0]
         self.x_in = torch.zeros(B, 1, rwkv.args.n_embd, device=p.device, dtype=p.dtype)
         if sampled:
             from . import sampling
-            self.pick = sampling.PickBuffers(B, p.device)      # params, u, token, logit_prob at fixed addresses
+            # params, u, token, logit_prob (and the counts) at fixed addresses
+            self.pick = sampling.PickBuffers(B, p.device, V=rwkv.emb.weight.size(0) if penalised else None)
 
             def step():
                 logits, _ = rwkv.forward_stateful(self.x_in, state, last_only=True)
                 if not sampling.kernel_supported(logits, rwkv.emb.weight, self.x_in):
                     raise RuntimeError("GraphDecoder(sampled=True): the pick kernel takes bf16 logits of a vocabulary that is a multiple of 8 "
                                        f"and at most {sampling.MAX_V}, and a bf16 embedding (got {tuple(logits.shape)} {logits.dtype})")
-                sampling.launch_pick(logits, self.pick, rwkv.emb.weight, self.x_in)
+                sampling.launch_pick(logits, self.pick, rwkv.emb.weight, self.x_in, self.pick.occ)
                 return logits
         else:
             def step():
@@ -741,6 +747,8 @@ class GraphDecoder:
         for dst, src in zip(state.att_x + state.ffn_x + state.S, keep):
             dst.copy_(src)
         state.fresh, state.n_tokens = fresh, n_tok
+        if penalised:
+            self.pick.reset()                                # warm-up and capture counted their tokens
 
     @torch.no_grad()
     def load_state(self, other: RWKV7State):

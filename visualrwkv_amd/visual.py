@@ -555,35 +555,60 @@ class VisualRWKV(nn.Module):
         return u.to(device=device, dtype=torch.float32)
 
     @staticmethod
-    def _sampled_append(out, triple, done, stop_token_idx):
+    def _stop_set(stop_token_idx):
+        """stop_token_idx as the set of tokens that end a run: an int, or a sequence of ints (the applications stop on [0, 261])."""
+        return frozenset(stop_token_idx) if isinstance(stop_token_idx, (list, tuple, set, frozenset)) else frozenset((stop_token_idx,))
+
+    @staticmethod
+    def _sampled_append(out, triple, done, stops):
         """One step's (token, logit, prob) rows into the result lists -- scalars for one row, lists of B values otherwise -- and whether
-        the call is over: every row has produced the stop token."""
+        the call is over: every row has produced a stop token."""
         tok, lg, pr = (t.tolist() for t in triple)
         for lst, v in zip(out, (tok, lg, pr)):
             lst.append(v[0] if len(v) == 1 else v)
         for b, t in enumerate(tok):
-            done[b] = done[b] or t == stop_token_idx
+            done[b] = done[b] or t in stops
         return all(done)
 
+    def _penalty_args(self, do_sample, temperature, top_p, presence_penalty, count_penalty, penalty_decay, token_ban):
+        """The sampling arguments of generate / generate_stateful, checked; returns whether the call needs occurrence counts."""
+        from . import sampling
+        token_ban = tuple(token_ban)
+        pen = sampling.penalised(presence_penalty, count_penalty, token_ban)
+        if pen and not do_sample:
+            raise ValueError("presence / count penalties and token_ban go with do_sample=True (the reference's applications sample; "
+                             "top_p=0 is greedy decoding under them)")
+        if do_sample:
+            sampling.check_args(temperature, top_p, presence_penalty, count_penalty, penalty_decay, token_ban, self.rwkv.emb.weight.size(0))
+        return pen
+
     @torch.no_grad()
-    def generate(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx, generator=None):
+    def generate(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx, generator=None,
+                 presence_penalty=0.0, count_penalty=0.0, penalty_decay=0.996, token_ban=()):
         """Decoding with the reference's semantics (src/model.py:496-530): the full sequence is re-run for every new token (stateful
         decoding is SURVEY.md 8f rank 1).  Greedy, or with do_sample the top-p / temperature pick of sampling.py on each step's last row
-        (the reference raises there; its applications sample); generator: the torch.Generator of the call's uniform numbers."""
+        (the reference raises there; its applications sample); generator: the torch.Generator of the call's uniform numbers.
+        presence_penalty, count_penalty, penalty_decay, token_ban: the applications' loop around the pick (v7.10/app/app_gpu.py:56-86;
+        sampling.py), do_sample only.  stop_token_idx: an int or a sequence of ints."""
+        pen = self._penalty_args(do_sample, temperature, top_p, presence_penalty, count_penalty, penalty_decay, token_ban)
+        stops = self._stop_set(stop_token_idx)
         samples = {"input_ids": input_ids, "images": images, "labels": torch.full_like(input_ids, IGNORE_INDEX)}
         if do_sample:
             from . import sampling
-            sampling.check_args(temperature, top_p)
             x, _, mk, _ = _embed(self, samples)
             mk.pop("n_image", None)
             B = x.size(0)
             u_all = self._sample_uniforms(max_new_tokens, B, generator, x.device)
             out, done = ([], [], []), [False] * B
+            occ = None
             for i in range(max_new_tokens):
                 logits = self.rwkv(x, **mk)[:, -1, :].contiguous()
                 nxt = torch.empty(B, 1, x.size(-1), device=x.device, dtype=x.dtype)
-                triple = sampling.pick(logits, temperature, top_p, u_all[i], self.rwkv.emb.weight.to(x.dtype), nxt)
-                if self._sampled_append(out, triple, done, stop_token_idx):
+                if pen and occ is None:
+                    occ = sampling.reset_occ(torch.empty(logits.shape, device=logits.device, dtype=torch.float32), token_ban)
+                triple = sampling.pick(logits, temperature, top_p, u_all[i], self.rwkv.emb.weight.to(x.dtype), nxt,
+                                       occ, presence_penalty, count_penalty, penalty_decay)
+                if self._sampled_append(out, triple, done, stops):
                     break
                 x = torch.cat((x, nxt), dim=-2)[:, -self.args.ctx_len:, :]
                 if "mask" in mk:
@@ -598,7 +623,7 @@ class VisualRWKV(nn.Module):
             toks.append(nxt.item())
             lgs.append(logits.gather(-1, nxt).item())
             prs.append(torch.softmax(logits, dim=-1).gather(-1, nxt).item())
-            if toks[-1] == stop_token_idx:
+            if toks[-1] in stops:
                 break
             x = torch.cat((x, self.rwkv.emb(nxt)), dim=-2)[:, -self.args.ctx_len:, :]
             if "mask" in mk:                                 # a generated token is text (v7.10 src/model.py:562-563)
@@ -607,7 +632,7 @@ class VisualRWKV(nn.Module):
 
     @torch.no_grad()
     def generate_stateful(self, input_ids, images, do_sample, temperature, top_p, max_new_tokens, stop_token_idx,
-                          use_graph=None, generator=None):
+                          use_graph=None, generator=None, presence_penalty=0.0, count_penalty=0.0, penalty_decay=0.996, token_ban=()):
         """`generate` with the recurrent state carried between tokens: one prefill over the prompt, then one
         single-token step per new token (O(1) per token instead of re-running the whole sequence).
         The prompt is left-padded once, like `RWKV.forward` pads it (src/model.py:301-307), so the first token
@@ -616,7 +641,10 @@ class VisualRWKV(nn.Module):
         do_sample: the pick of sampling.py instead of the argmax, with the call's uniform numbers drawn up front from `generator`.  Through
         the captured graph (bf16, fused, B <= 4) the pick is the step's last kernel and writes the next input itself: a token is one
         replay and one read-back; otherwise sampling.pick per token.  Several rows: every list entry holds B values, and the call ends
-        when every row has produced the stop token."""
+        when every row has produced a stop token (stop_token_idx: an int or a sequence of ints).
+        presence_penalty, count_penalty, penalty_decay, token_ban (do_sample only): the occurrence counts live on the device beside the
+        decoder, the graph's last kernel is the penalised pick (GraphDecoder(penalised=True)), and a token still costs one replay and one
+        read-back; with all of them at their defaults the call is exactly the unpenalised one."""
         if getattr(self, "vrwkv", None) is not None:
             raise NotImplementedError("generate_stateful with args.n_vrwkv_layer: only the embedding differs, but the stateful path has not been "
                                       "shown equal to generate() with the vision encoder in front of it; use generate()")
@@ -625,6 +653,8 @@ class VisualRWKV(nn.Module):
                                       "with two experts the next token needs that row under its own expert's LayerNorm (ln2 or ln_v), so the carried "
                                       "row would have to be re-normed per expert; use generate()")
         from .rwkv7 import CHUNK_LEN
+        pen = self._penalty_args(do_sample, temperature, top_p, presence_penalty, count_penalty, penalty_decay, token_ban)
+        stops = self._stop_set(stop_token_idx)
         samples = {"input_ids": input_ids, "images": images, "labels": torch.full_like(input_ids, IGNORE_INDEX)}
         x, _ = self.preparing_embedding(samples)
         x = x[:, -self.args.ctx_len:, :]
@@ -635,7 +665,8 @@ class VisualRWKV(nn.Module):
             use_graph = (x.is_cuda and bool(getattr(self.args, "fused", False)) and x.dtype == torch.bfloat16 and x.size(0) <= 4
                          and max_new_tokens >= 8)
         if do_sample:
-            return self._generate_stateful_sampled(logits, state, temperature, top_p, max_new_tokens, stop_token_idx, use_graph, generator)
+            return self._generate_stateful_sampled(logits, state, temperature, top_p, max_new_tokens, stops, use_graph, generator,
+                                                   (presence_penalty, count_penalty, penalty_decay, tuple(token_ban)) if pen else None)
         decoder = self.rwkv.decoder_for(state) if use_graph and x.is_cuda else None     # one capture per batch size, re-used
         toks, lgs, prs = [], [], []
         for _ in range(max_new_tokens):
@@ -643,7 +674,7 @@ class VisualRWKV(nn.Module):
             toks.append(nxt.item())
             lgs.append(logits.gather(-1, nxt).item())
             prs.append(torch.softmax(logits, dim=-1).gather(-1, nxt).item())
-            if toks[-1] == stop_token_idx or len(toks) == max_new_tokens:
+            if toks[-1] in stops or len(toks) == max_new_tokens:
                 break
             if decoder is not None:
                 logits = decoder(self.rwkv.emb(nxt))
@@ -651,29 +682,33 @@ class VisualRWKV(nn.Module):
                 logits, state = self.rwkv.forward_stateful(self.rwkv.emb(nxt), state, last_only=True)
         return toks, lgs, prs
 
-    def _generate_stateful_sampled(self, logits, state, temperature, top_p, max_new_tokens, stop_token_idx, use_graph, generator):
+    def _generate_stateful_sampled(self, logits, state, temperature, top_p, max_new_tokens, stops, use_graph, generator, pen=None):
+        """pen: None, or (presence, count, decay, token_ban) of a call that needs occurrence counts."""
         from . import sampling
-        sampling.check_args(temperature, top_p)
         B = logits.size(0)
+        presence, count, decay, token_ban = pen if pen is not None else (0.0, 0.0, 0.996, ())
         emb = self.rwkv.emb.weight
         u_all = self._sample_uniforms(max_new_tokens, B, generator, logits.device)
         logits = logits.contiguous()
         use_graph = bool(use_graph) and logits.is_cuda and sampling.kernel_supported(logits, emb)
         out, done = ([], [], []), [False] * B
         if use_graph:
-            decoder = self.rwkv.decoder_for(state, sampled=True)
-            decoder.pick.set(temperature, top_p)
-            # the first token eagerly, from the prefill's logits, into the graph's input
-            triple = sampling.pick(logits, temperature, top_p, u_all[0], emb, decoder.x_in)
+            decoder = self.rwkv.decoder_for(state, sampled=True, penalised=pen is not None)
+            decoder.pick.set(temperature, top_p, presence, count, decay)
+            if pen is not None:
+                decoder.pick.reset(token_ban)
+            # the first token eagerly, from the prefill's logits, into the graph's input (and the graph's counts)
+            triple = sampling.pick(logits, temperature, top_p, u_all[0], emb, decoder.x_in, decoder.pick.occ, presence, count, decay)
             for i in range(1, max_new_tokens + 1):
-                if self._sampled_append(out, triple, done, stop_token_idx) or i == max_new_tokens:
+                if self._sampled_append(out, triple, done, stops) or i == max_new_tokens:
                     break
                 triple = decoder.sample(u_all[i])
             return out
         nxt = torch.empty(B, 1, emb.size(1), device=logits.device, dtype=logits.dtype)
+        occ = sampling.reset_occ(torch.empty(logits.shape, device=logits.device, dtype=torch.float32), token_ban) if pen is not None else None
         for i in range(max_new_tokens):
-            triple = sampling.pick(logits, temperature, top_p, u_all[i], emb.to(logits.dtype), nxt)
-            if self._sampled_append(out, triple, done, stop_token_idx) or i == max_new_tokens - 1:
+            triple = sampling.pick(logits, temperature, top_p, u_all[i], emb.to(logits.dtype), nxt, occ, presence, count, decay)
+            if self._sampled_append(out, triple, done, stops) or i == max_new_tokens - 1:
                 break
             logits, state = self.rwkv.forward_stateful(nxt, state, last_only=True)
             logits = logits.contiguous()
